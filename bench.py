@@ -22,13 +22,21 @@ Prints ONE JSON line on rank 0.  `roofline.achieved` = (C + D algorithmic
 bytes per decode) / the pipeline's average device time, measured with HIP
 events on the launches' stream inside the timed region; `traffic` is the
 HBM bytes per decode measured by rocprofv3 FETCH_SIZE/WRITE_SIZE passes
-(profiles/pmc_latest.json, tools/profile.sh).  On one GPU the line also
-carries `workloads` (the E.coli-tiled and i.i.d. kjv-unigram streams of the
-same size) and `evaluate` (the reference's evaluate() scope:
-host payload in, host symbols out).  `cpu_baseline` times the reference's
+(profiles/pmc_latest.json, tools/profile.sh).
+
+A plain run does only what that headline needs: set-up, the checked
+decode, the warm-up, the timed steps, the line.  `--dump-outputs DIR` also
+writes what the last timed step decoded (dump_outputs).  `--full` (one GPU)
+adds everything else, outside the timed region: `ms_per_call_sync`, the
+two-pass kernel split and the streaming-copy rate in `roofline`,
+`workloads` (the E.coli-tiled and i.i.d. kjv-unigram streams of the
+same size), `evaluate` (the reference's evaluate() scope:
+host payload in, host symbols out), `encode`, and `cpu_baseline`, which
+times the reference's
 own linApproach (oracle/_ref, compiled from the reference's C sources) or,
 if that was not built, the oracle's restatement, on a bounded sample
-(kjv.txt.huff) on one host core.
+(kjv.txt.huff) on one host core.  `--no-extra` and `--no-cpu-baseline`
+leave parts of `--full` out.
 """
 from __future__ import annotations
 
@@ -53,6 +61,12 @@ def _args():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size-mib", type=int, default=1024, help="compressed MiB per GPU")
     ap.add_argument("--files", default=os.path.join(ROOT, "files"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, everything else this benchmark measures (one GPU): the "
+                         "synchronous call's latency, the two-pass kernel split, the streaming-copy rate, "
+                         "the other workloads, the evaluate() scope, the encoder and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step decoded as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-extra", action="store_true",
@@ -63,7 +77,10 @@ def _args():
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo: tests)")
     ap.add_argument("--one-device", action="store_true",
                     help="every rank on cuda:0 (tests of the N > 1 path on a one-GPU box; gloo only)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def cpu_baseline(files_dir: str, seconds: float, name: str = "kjv.txt.huff") -> dict:
@@ -378,6 +395,47 @@ def load_pmc(path: str, workload: str):
     return None
 
 
+DUMP_SEED = 0xD0C5EED
+DUMP_WHOLE = 1 << 22       # outputs up to this many symbols are written whole
+DUMP_EDGE = 1 << 20        # symbols kept from each end of a larger output
+DUMP_SAMPLE = 1 << 22      # symbols sampled from a larger output
+DUMP_BLOCK = 1 << 20       # symbols per block sum
+
+
+def dump_outputs(out_dir: str, out, n: int, tag: str = "") -> None:
+    """--dump-outputs: what a caller of the timed decode receives -- the
+    decoded length and the symbols out[:n] -- as out_dir/<name><tag>.npy:
+
+      decoded_length   float64[1]   n
+      decoded_symbols  float32      out[:n] whole if n <= DUMP_WHOLE; otherwise
+                                    its first and last DUMP_EDGE symbols around
+                                    DUMP_SAMPLE symbols at sorted positions drawn
+                                    once from numpy's default_rng(DUMP_SEED)
+      decoded_block_sums float64    the sum of every DUMP_BLOCK symbols of
+                                    out[:n] (the last block shorter): exact
+                                    integers, every symbol counted
+
+    about 24 MB for the 1 GiB stream.  The positions depend on n alone, so two
+    builds that decode the same stream write arrays that compare element for
+    element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sym = out[:n]
+    if n <= DUMP_WHOLE:
+        keep = sym
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(DUMP_EDGE, n - DUMP_EDGE, DUMP_SAMPLE))
+        keep = torch.cat([sym[:DUMP_EDGE], sym[torch.from_numpy(pos).to(sym.device)], sym[n - DUMP_EDGE:]])
+    whole = n // DUMP_BLOCK * DUMP_BLOCK
+    sums = [sym[:whole].view(whole // DUMP_BLOCK, DUMP_BLOCK).sum(dim=1, dtype=torch.int64)]
+    if whole < n:
+        sums.append(sym[whole:].sum(dtype=torch.int64).reshape(1))
+    np.save(os.path.join(out_dir, f"decoded_length{tag}.npy"), np.array([n], np.float64))
+    np.save(os.path.join(out_dir, f"decoded_symbols{tag}.npy"), keep.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, f"decoded_block_sums{tag}.npy"), torch.cat(sums).to(torch.float64).cpu().numpy())
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -475,7 +533,8 @@ def main():
     # (collectives over host tensors with gloo)
     red_dev = torch.device("cpu") if world > 1 and a.backend == "gloo" else dev
     sync_ms = None
-    if world == 1:
+    full = a.full and world == 1
+    if full:
         # the synchronous call (hh_decode_device: returns once the length is
         # known) timed on its own, for the per-call latency
         ts = []
@@ -484,6 +543,9 @@ def main():
             run_step()
             ts.append(time.perf_counter() - t1)
         sync_ms = statistics.median(ts) * 1e3
+    if a.dump_outputs:
+        # what gets written is what the timed steps decode, not the warm-up's
+        (job.out if world > 1 else out).zero_()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -522,8 +584,14 @@ def main():
 
     ms_step = elapsed / a.steps * 1e3
     ms_dev = statistics.mean(s["ms_total"] for s in dev_ms)
-    # the split by kernel from a separate phase-timed decoder (world 1)
-    phases = (phase_split(local, syn.tree, 0, syn.data, syn.bits, out) if world == 1
+    if a.dump_outputs:
+        # the last timed step's output, before anything else decodes
+        if world > 1:
+            dump_outputs(a.dump_outputs, job.out, job.decoded_bytes, f"_rank{rank}")
+        else:
+            dump_outputs(a.dump_outputs, out, int(lens[-1].value))
+    # the split by kernel from a separate phase-timed decoder (--full)
+    phases = (phase_split(local, syn.tree, 0, syn.data, syn.bits, out) if full
               else {"sync": None, "scan": None, "emit": None})
     fast = all(s["exact_fallback"] == 0 for s in dev_ms)
     kernels = ("k_one" if all(s["state_machine"] == 2 for s in dev_ms)
@@ -596,13 +664,13 @@ def main():
         "single_pass": all(s["state_machine"] == 2 for s in dev_ms),
     }
     res.update(extra)
-    if world == 1:
+    if full:
         # the same box's streaming rate over the same bytes (after the timed region)
         cp = copy_rate(dev, (C_bytes + D_bytes) // 2)
         res["roofline"]["copy_GBps"] = cp["GBps"]
         res["roofline"]["copy"] = cp
         res["roofline"]["frac_vs_copy"] = round(achieved / cp["GBps"], 4)
-    if world == 1 and not a.no_extra:
+    if full and not a.no_extra:
         # SURVEY 8d's other single-GPU configs and the evaluate() scope
         # (after the headline measurement, outside its timed region)
         import numpy as np
@@ -667,7 +735,7 @@ def main():
         torch.cuda.empty_cache()
         res["workloads"] = more
         res["encode"] = encode_rate(H, hf, text, syn.decoded_bytes, dev)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and full and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(a.files, a.cpu_seconds)
         from oracle import oracle as O
         if O.ref_available():

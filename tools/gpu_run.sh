@@ -14,7 +14,7 @@ if [ "$WHAT" = tests ] || [ "$WHAT" = all ]; then
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
   echo "[$(date +%T)] bench"
-  timeout -k 10 600 python3 bench.py > $E/bench.json 2> $E/bench.err || { tail -20 $E/bench.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > $E/bench.json 2> $E/bench.err || { tail -20 $E/bench.err; exit 1; }
   cat $E/bench.json
 fi
 echo "[$(date +%T)] done"

@@ -18,7 +18,7 @@ bash tools/profile.sh $TAG > $E/profile.log 2>&1 || { tail -20 $E/profile.log; e
 python3 tools/prof_summary.py $TAG > $E/prof_summary.log 2>&1 || exit 1
 cp profiles/${TAG}_kernels.json profiles/${TAG}_kernel_stats.csv profiles/pmc_latest.json $E/
 echo "[$(date +%T)] bench"
-timeout -k 10 600 python3 bench.py > $E/${TAG}_bench_latest.json 2> $E/bench.err || { tail -20 $E/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $E/${TAG}_bench_latest.json 2> $E/bench.err || { tail -20 $E/bench.err; exit 1; }
 cat $E/${TAG}_bench_latest.json
 echo "[$(date +%T)] bench under a kernel trace"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $E/kt_bench -o run -- python3 bench.py --no-extra --no-cpu-baseline > $E/${TAG}_bench_traced.json 2> $E/kt_bench.err || { tail -20 $E/kt_bench.err; exit 1; }

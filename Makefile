@@ -48,13 +48,19 @@ $(BUILD)/hh_fsm.o: $(CSRC)/hh_fsm.hip $(CSRC)/hh_fsm_kern.h $(CSRC)/hh_fsm_dev.h
                    $(CSRC)/hh_internal.h include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/hh_encode.o: $(CSRC)/hh_encode.hip $(CSRC)/hh_internal.h include/hiphuff.h | $(BUILD)
+$(BUILD)/hh_encode.o: $(CSRC)/hh_encode.hip $(CSRC)/hh_internal.h $(CSRC)/hh_enc.h include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/hh_hist.o: $(CSRC)/hh_hist.hip $(CSRC)/hh_hist_kern.h $(CSRC)/hh_enc.h include/hiphuff.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/hh_build.o: $(CSRC)/hh_build.c include/hiphuff.h | $(BUILD)
+	$(CC) $(CFLAGS) -c $< -o $@
 
 $(BUILD)/hh_probe.o: $(CSRC)/hh_probe.hip include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/hh_device.o $(BUILD)/hh_fsm.o $(BUILD)/hh_one.o $(BUILD)/hh_encode.o $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o $(BUILD)/hh_plugin.o
+$(LIB): $(BUILD)/hh_device.o $(BUILD)/hh_fsm.o $(BUILD)/hh_one.o $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 $(CLI): $(PKG)/host/hh_cli.c $(LIB) include/hiphuff.h include/hiphuff_plugin.h
@@ -66,7 +72,10 @@ oracle:
 
 # microbenchmarks the profiling scripts run (tools/profile.sh: FETCH_SIZE
 # calibration on known byte counts)
-ubench: $(BUILD)/ub_fetch
+ubench: $(BUILD)/ub_fetch $(BUILD)/ub_hist
+# the histogram kernel's LDS copies x workgroups per CU (DESIGN.md "Compression")
+$(BUILD)/ub_hist: tools/ubench/ub_hist.hip $(CSRC)/hh_hist_kern.h | $(BUILD)
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -I$(CSRC) -o $@ $<
 $(BUILD)/ub_fetch: tools/ubench/ub_fetch.hip | $(BUILD)
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $<
 
@@ -81,7 +90,7 @@ clean:
 
 # A/B variant of the library: make variant V=name HIPEXTRA="-DHH_X=1"
 # -> build/libhiphuff_<name>.so (tools/ab.sh)
-variant: $(BUILD)/hh_plugin.o $(BUILD)/hh_encode.o $(BUILD)/hh_probe.o
+variant: $(BUILD)/hh_plugin.o $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_build.o $(BUILD)/hh_probe.o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_device.hip -o $(BUILD)/hh_device_$(V).o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_fsm.hip -o $(BUILD)/hh_fsm_$(V).o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_one.hip -o $(BUILD)/hh_one_$(V).o

@@ -51,6 +51,14 @@ class _Tree(C.Structure):
                 ("sym", C.c_void_p)]
 
 
+BUILD_MAX_NODES = 511   # HH_BUILD_MAX_NODES
+
+
+class _TreeBuf(C.Structure):
+    _fields_ = [("nodes", C.c_int32), ("izero", C.c_int32 * BUILD_MAX_NODES),
+                ("ione", C.c_int32 * BUILD_MAX_NODES), ("sym", C.c_uint8 * BUILD_MAX_NODES)]
+
+
 class _TreeInfo(C.Structure):
     _fields_ = [("reachable", C.c_int32), ("leaves", C.c_int32), ("minlen", C.c_int32),
                 ("maxlen", C.c_int32), ("len_gcd", C.c_int32)]
@@ -104,6 +112,11 @@ _SIGS = {
     "hh_encoder_destroy": ([C.c_void_p], None),
     "hh_encoder_encode": ([C.c_void_p, C.POINTER(_Tree), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                            C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
+    "hh_tree_build": ([C.POINTER(C.c_uint64), C.POINTER(_TreeBuf)], C.c_int),
+    "hh_histogram_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
+    "hh_compress_bound": ([C.c_uint64], C.c_uint64),
+    "hh_compress_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_TreeBuf),
+                            C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
     "hh_decoder_create": ([C.POINTER(C.c_void_p), C.POINTER(_Config)], C.c_int),
     "hh_decoder_destroy": ([C.c_void_p], None),
     "hh_decoder_set_tree": ([C.c_void_p, C.POINTER(_Tree)], C.c_int),
@@ -239,6 +252,33 @@ class Tree:
         self._c = _Tree(len(self.izero), self.izero.ctypes.data, self.ione.ctypes.data,
                         self.sym.ctypes.data)
 
+    @classmethod
+    def _from_buf(cls, tb: "_TreeBuf") -> "Tree":
+        n = tb.nodes
+        return cls(np.array(tb.izero[:n], np.int32), np.array(tb.ione[:n], np.int32),
+                   np.array(tb.sym[:n], np.uint8))
+
+    @classmethod
+    def from_counts(cls, counts) -> "Tree":
+        """The Huffman tree of byte counts (hh_tree_build; up to 256 of them,
+        the rest zero): node for node what synth.huffman_tree builds."""
+        c = np.zeros(256, np.uint64)
+        given = np.asarray(counts)
+        if given.ndim != 1 or given.size > 256:
+            raise ValueError("counts: a vector of at most 256 entries")
+        if given.dtype.kind not in "ui":
+            # (Python ints beyond int64 arrive as floats or objects: exact through int())
+            vals = [int(v) for v in counts]
+            if any(v != w for v, w in zip(vals, counts)):
+                raise ValueError("counts: integers")
+            given = np.array(vals, dtype=object)
+        if given.size and (min(given.tolist()) < 0 or max(given.tolist()) >= 1 << 64):
+            raise ValueError("counts: entries in [0, 2^64)")
+        c[: given.size] = given.astype(np.uint64)
+        tb = _TreeBuf()
+        _check(lib().hh_tree_build(c.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(tb)), "tree build")
+        return cls._from_buf(tb)
+
     def info(self) -> dict:
         inf = _TreeInfo()
         _check(lib().hh_tree_check(C.byref(self._c), C.byref(inf)), "tree check")
@@ -289,6 +329,39 @@ class Encoder:
                "encoder_encode")
         return int(bits.value)
 
+    def histogram(self, syms, stream=None) -> np.ndarray:
+        """Exact byte counts (np.uint64[256]) of the torch uint8 CUDA tensor
+        syms (hh_histogram_device; any alignment), on stream (default: the
+        current one)."""
+        import torch
+        assert syms.is_cuda and syms.dtype == torch.uint8 and syms.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(syms.device)
+        counts = np.zeros(256, np.uint64)
+        _check(lib().hh_histogram_device(self._h, syms.data_ptr() if syms.numel() else None, syms.numel(),
+                                         counts.ctypes.data_as(C.POINTER(C.c_uint64)), s.cuda_stream), "histogram")
+        return counts
+
+    def compress(self, syms, out, stream=None) -> tuple:
+        """Histogram, tree build and encode in one call (hh_compress_device):
+        syms compressed into out (both torch uint8 CUDA tensors; out holds
+        compress_bound(n) bytes, plus PAYLOAD_PAD for a decode) with their own
+        Huffman code.  Returns (Tree, bits).  A HipHuffError of status -5
+        (capacity) carries .tree and .bits."""
+        import torch
+        assert syms.is_cuda and out.is_cuda and syms.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert syms.is_contiguous() and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(syms.device)
+        tb = _TreeBuf()
+        bits = C.c_uint64(0)
+        rc = lib().hh_compress_device(self._h, syms.data_ptr() if syms.numel() else None, syms.numel(),
+                                      out.data_ptr(), out.numel(), C.byref(tb), C.byref(bits), s.cuda_stream)
+        if rc == -5:
+            e = HipHuffError(rc, "compress")
+            e.tree, e.bits = Tree._from_buf(tb), int(bits.value)
+            raise e
+        _check(rc, "compress")
+        return Tree._from_buf(tb), int(bits.value)
+
     def close(self):
         if self._h:
             lib().hh_encoder_destroy(self._h)
@@ -299,6 +372,37 @@ class Encoder:
             self.close()
         except Exception:
             pass
+
+
+def compress_bound(n: int) -> int:
+    """hh_compress_bound: bytes that always hold n symbols' stream."""
+    return int(lib().hh_compress_bound(n))
+
+
+def histogram_device(syms, stream=None) -> np.ndarray:
+    """Encoder.histogram on a temporary encoder of syms' device."""
+    enc = Encoder(syms.device.index or 0)
+    try:
+        return enc.histogram(syms, stream)
+    finally:
+        enc.close()
+
+
+def compress_device(syms, stream=None) -> "HuffFile":
+    """The torch uint8 CUDA tensor syms as a .huff container, compressed on
+    the GPU with its own Huffman code (Encoder.compress); the payload is
+    copied to the host."""
+    import torch
+    n = syms.numel()
+    out = torch.zeros(compress_bound(n) + PAYLOAD_PAD, dtype=torch.uint8, device=syms.device)
+    enc = Encoder(syms.device.index or 0)
+    try:
+        tree, bits = enc.compress(syms, out, stream)
+    finally:
+        enc.close()
+    data = out[: (bits + 7) // 8 + PAYLOAD_PAD].cpu().numpy()
+    data[(bits + 7) // 8:] = 0
+    return HuffFile(tree.izero, tree.ione, tree.sym, bits, n, data)
 
 
 def copy_device(src, dst, nt: bool = False, stream=None) -> float:

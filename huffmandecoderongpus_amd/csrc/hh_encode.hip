@@ -23,6 +23,7 @@
 
 #include "hiphuff.h"
 #include "hh_internal.h"
+#include "hh_enc.h"
 
 #define ENC_TB 256                 // threads per workgroup
 #define ENC_PT 16                  // symbols per thread
@@ -180,17 +181,7 @@ __global__ __launch_bounds__(ENC_TB) void k_enc_pack(const uint8_t *__restrict__
     }
 }
 
-// An encoder: the workspace of one device's encodes (the table, the chunks'
-// bits / offsets, the total and the absent-symbol flag), kept across calls
-// and grown when a call needs more.  Calls on one encoder run one at a time
-// (each returns when its encode is done); encoders are independent, so
-// encodes on several streams run at once with one encoder each.
-struct hh_encoder {
-    int device;
-    uint8_t *ws;
-    size_t size;
-};
-
+// (struct hh_encoder: hh_enc.h)
 extern "C" int hh_encoder_create(hh_encoder **enc, int device) {
     if (!enc) return HH_ERR_ARG;
     *enc = nullptr;
@@ -208,6 +199,10 @@ extern "C" void hh_encoder_destroy(hh_encoder *enc) {
     if (enc->ws) {
         (void)hipSetDevice(enc->device);
         (void)hipFree(enc->ws);                        // (every encode on it has returned: nothing in flight)
+    }
+    if (enc->hist_ws) {
+        (void)hipSetDevice(enc->device);
+        (void)hipFree(enc->hist_ws);
     }
     free(enc);
 }
@@ -284,4 +279,41 @@ extern "C" int hh_encode_device(const hh_tree *tree, const void *d_syms, uint64_
         if (rc) return rc;
     }
     return hh_encoder_encode(s_enc[dev], tree, d_syms, n, d_out, cap, bits, hip_stream);
+}
+
+// Compress: bytes in HBM -> tree + stream, the data never leaving the GPU.
+// Histogram (csrc/hh_hist.hip), tree build on the host (csrc/hh_build.c),
+// then the encode above with that tree.  The host knows the stream's length
+// (sum of count x code length) before any encode kernel runs: the capacity
+// check is made there, and the encoder's own total must agree afterwards (a
+// histogram miscount that happens to leave the tree unchanged would show
+// here).
+// The bound: a Huffman code over at most 256 symbols is never longer than
+// the fixed 8-bit code (bits <= 8 n; one distinct symbol: bits == n), and
+// the encoder writes whole 32-bit words.
+extern "C" uint64_t hh_compress_bound(uint64_t n) { return (n + 3) / 4 * 4; }
+
+extern "C" int hh_compress_device(hh_encoder *enc, const void *d_syms, uint64_t n, void *d_out, uint64_t cap,
+                                  hh_tree_buf *tree, uint64_t *bits, void *hip_stream) {
+    if (!enc || !d_syms || !tree || !bits || n == 0 || (!d_out && cap)) return HH_ERR_ARG;
+    if (((uintptr_t)d_out & 3u) != 0) return HH_ERR_ARG;   // (32-bit word stores)
+    *bits = 0;
+    uint64_t counts[256];
+    int rc = hh_histogram_device(enc, d_syms, n, counts, hip_stream);
+    if (rc) return rc;
+    rc = hh_tree_build(counts, tree);
+    if (rc) return rc;
+    const hh_tree t = {tree->nodes, tree->izero, tree->ione, tree->sym};
+    uint64_t code[256];
+    uint8_t len8[256];
+    rc = hh_codebook(&t, code, len8);
+    if (rc) return rc;
+    uint64_t pred = 0;
+    for (int s = 0; s < 256; s++) pred += counts[s] * len8[s];   // (<= 64 n < 2^43)
+    *bits = pred;
+    if ((pred + 31) / 32 * 4 > cap) return HH_ERR_CAPACITY;
+    uint64_t got = 0;
+    rc = hh_encoder_encode(enc, &t, d_syms, n, d_out, cap, &got, hip_stream);
+    if (rc) return rc;
+    return got == pred ? HH_OK : HH_ERR_INTERNAL;
 }

@@ -12,6 +12,13 @@
  * more times; the minimum is printed in the reference's format
  * "%17s %8s     %.9f ms" (mainrun.c:412-420).  DIR defaults to
  * $HIPHUFF_FILES or ./files.
+ *
+ *   HuffFramework compress <in> <out.huff>
+ *
+ * compresses a file on the GPU (hh_compress_device: histogram, tree build,
+ * encode), decodes the stream again and compares it with the input, writes
+ * the container (HUFX when the sizes need it) and prints the reference's
+ * "nodes, bits, uncompressedsize" line (mainrun.c:475-478).
  */
 #define _GNU_SOURCE
 #include <stdint.h>
@@ -177,13 +184,15 @@ static void graphtest(decode_fn fn, const char *dname, const testdata *td, uint6
 }
 
 static int dec_stages(const testdata *td, uint64_t bits, uint8_t *out, uint64_t cap, uint64_t *n);
+static int run_compress(const char *in, const char *outp);
 
 int main(int argc, char **argv) {
     const char *test = argc > 1 ? argv[1] : "hello";
-    const char *arg2 = NULL;
+    const char *arg2 = NULL, *arg3 = NULL;
     for (int i = 2; i < argc; i++) {
         if (!strcmp(argv[i], "--files") && i + 1 < argc) g_dir = argv[++i];
         else if (!strcmp(argv[i], "--reps") && i + 1 < argc) g_reps = atoi(argv[++i]);
+        else if (!strcmp(test, "compress") && arg2) arg3 = argv[i];
         else arg2 = argv[i];
     }
     const char *env = getenv("HIPHUFF_FILES");
@@ -229,6 +238,8 @@ int main(int argc, char **argv) {
         if (load_test(&td, arg2, arg2)) return 1;
         evalandshow(dec_stages, "hipstages", &td);
         free_test(&td);
+    } else if (!strcmp(test, "compress") && arg2 && arg3) {
+        if (run_compress(arg2, arg3)) { hh_decoder_destroy(g_dec); return 1; }
     } else {
         fprintf(stderr, "unknown test %s\n", test);
         hh_decoder_destroy(g_dec);
@@ -251,4 +262,59 @@ static int dec_stages(const testdata *td, uint64_t bits, uint8_t *out, uint64_t 
     (void)hipFree(dd);
     (void)hipFree(dout);
     return rc;
+}
+
+/* compress <in> <out.huff>: the file's bytes to the device, hh_compress_device,
+ * the stream decoded again (hh_decode_host) and compared with the input, then
+ * the container written. */
+static int run_compress(const char *in, const char *outp) {
+    FILE *f = fopen(in, "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", in); return 1; }
+    fseek(f, 0, SEEK_END);
+    long flen = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    if (flen <= 0) { fprintf(stderr, "%s is empty\n", in); fclose(f); return 1; }
+    const uint64_t n = (uint64_t)flen, cap = hh_compress_bound(n);
+    uint8_t *orig = (uint8_t *)malloc(n), *back = (uint8_t *)calloc(n + 3, 1);
+    uint8_t *pay = (uint8_t *)calloc(cap + HH_PAYLOAD_PAD, 1);
+    void *d_in = NULL, *d_out = NULL;
+    hh_encoder *enc = NULL;
+    hh_tree_buf tb;
+    uint64_t bits = 0, m = 0;
+    int rc = HH_ERR_NOMEM, ok = 0;
+    do {
+        if (!orig || !back || !pay) break;
+        rc = HH_ERR_IO;
+        if (fread(orig, 1, n, f) != n) break;
+        rc = HH_ERR_NOMEM;
+        if (hipMalloc(&d_in, n) != hipSuccess || hipMalloc(&d_out, cap + HH_PAYLOAD_PAD) != hipSuccess) break;
+        rc = HH_ERR_DEVICE;
+        if (hipMemcpy(d_in, orig, n, hipMemcpyHostToDevice) != hipSuccess) break;
+        if ((rc = hh_encoder_create(&enc, 0)) != HH_OK) break;
+        if ((rc = hh_compress_device(enc, d_in, n, d_out, cap, &tb, &bits, NULL)) != HH_OK) break;
+        rc = HH_ERR_DEVICE;
+        if (hipMemcpy(pay, d_out, (bits + 7) / 8, hipMemcpyDeviceToHost) != hipSuccess) break;
+        hh_huff h = {tb.nodes, tb.izero, tb.ione, tb.sym, bits, n, pay, 0};
+        hh_tree t = hh_huff_tree(&h);
+        if ((rc = hh_decoder_set_tree(g_dec, &t)) != HH_OK) break;
+        if ((rc = hh_decode_host(g_dec, pay, bits, back, n + 3, &m)) != HH_OK) break;
+        if (compare(back, m, orig, n) != 0) {
+            fprintf(stderr, "problem with : compress (the stream does not decode to %s)\n", in);
+            rc = HH_ERR_INTERNAL;
+            break;
+        }
+        if ((rc = hh_huff_save(outp, &h)) != HH_OK) break;
+        printf("%s nodes %d, bits %llu, uncompressedsize %llu\n", in, h.nodes, (unsigned long long)h.bits,
+               (unsigned long long)h.uncompressedsize);
+        ok = 1;
+    } while (0);
+    if (!ok) fprintf(stderr, "compress %s: %s\n", in, hh_strerror(rc));
+    fclose(f);
+    hh_encoder_destroy(enc);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    free(orig);
+    free(back);
+    free(pay);
+    return ok ? 0 : 1;
 }

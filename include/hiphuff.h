@@ -8,6 +8,9 @@
  *
  * Layering
  *   hh_huff_*      .huff container (HUFF + 64-bit HUFX)     replaces huffdata.c:27-68
+ *   hh_encode*, hh_tree_build, hh_histogram_device, hh_compress_device
+ *                  the way back: bytes to a code and a stream (the reference
+ *                  ships none)
  *   hh_decoder_*   device decoder state (tables, workspace)  replaces the lazy CL/CUDA
  *                                                             globals, openclapproach.c:231-234
  *   hh_decode_*    the hot path                               replaces openclApproach
@@ -131,6 +134,52 @@ int hh_encoder_encode(hh_encoder *enc, const hh_tree *tree, const void *d_syms, 
  * serialised on it). */
 int hh_encode_device(const hh_tree *tree, const void *d_syms, uint64_t n,
                      void *d_out, uint64_t cap, uint64_t *bits, void *hip_stream);
+
+/* ---------------------------------------------------------------------- */
+/* Compression: from bytes to a code and a stream (the reference ships    */
+/* .huff files and no way to make one).                                   */
+/* ---------------------------------------------------------------------- */
+/* Huffman tree of byte counts, on the host.  Deterministic: the live items
+ * are the symbols with counts[s] > 0 (k of them); the two smallest keys
+ * (count, order) a then b are merged into a node of count a + b with
+ * zero-child a and one-child b, where a leaf's order is its symbol value and
+ * the i-th node created has order k + i (a leaf before a node of the same
+ * count and order).  Laid out in pre-order (node 0 the root, then the zero
+ * subtree, then the one subtree; internal nodes sym 0).  One distinct symbol
+ * s: three nodes, leaf s on the zero side and leaf (s + 1) & 255 on the one
+ * side (a root leaf is no tree, HH_ERR_TREE above).  HH_ERR_ARG: all counts
+ * zero, or their total overflows uint64_t.  No limit on the code length
+ * here; the encoders answer HH_ERR_UNSUPPORTED for codes over 64 bits
+ * (a code of depth d needs a total of about Fib(d + 1): the 2^36 symbols an
+ * encoder call takes cannot give one). */
+#define HH_BUILD_MAX_NODES 511
+typedef struct {
+    int32_t nodes;
+    int32_t izero[HH_BUILD_MAX_NODES];
+    int32_t ione[HH_BUILD_MAX_NODES];
+    uint8_t sym[HH_BUILD_MAX_NODES];
+} hh_tree_buf;
+int hh_tree_build(const uint64_t counts[256], hh_tree_buf *out);
+
+/* Exact counts of the n bytes at device pointer d_syms (any alignment) into
+ * counts[256] on the host.  Enqueued on hip_stream; returns when done.  The
+ * scratch is the encoder's (one call at a time per encoder).  n == 0: all
+ * zero.  At most about 2^36 bytes, as hh_encoder_encode. */
+int hh_histogram_device(hh_encoder *enc, const void *d_syms, uint64_t n,
+                        uint64_t counts[256], void *hip_stream);
+
+/* Histogram, hh_tree_build, hh_encoder_encode in one call: n > 0 bytes at
+ * d_syms compressed into d_out (cap bytes, 4-byte aligned) with their own
+ * Huffman code, which *tree receives; *bits the stream's length.
+ * hh_compress_bound(n) = n rounded up to 4 bytes always suffices (a Huffman
+ * code over bytes never exceeds 8 bits per symbol on average, and the encoder
+ * writes whole 32-bit words).  HH_ERR_CAPACITY is found before any encode
+ * kernel runs, *tree and *bits filled.  Add HH_PAYLOAD_PAD bytes to decode
+ * d_out in place. */
+uint64_t hh_compress_bound(uint64_t n);
+int hh_compress_device(hh_encoder *enc, const void *d_syms, uint64_t n,
+                       void *d_out, uint64_t cap, hh_tree_buf *tree,
+                       uint64_t *bits, void *hip_stream);
 
 /* ---------------------------------------------------------------------- */
 /* Device decoder.                                                        */

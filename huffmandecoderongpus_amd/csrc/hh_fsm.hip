@@ -884,8 +884,8 @@ __device__ __forceinline__ void fscan_final(const FsmGeo &geo, const FsmWork &wk
 // (flags[8]); the block whose add returns nblk - 1 -- the last adder, told
 // by the value its add returned -- reads them with sc1 loads (agent-scope
 // atomic loads), its other waves after a workgroup barrier.
-// (test_gpu_parity.py::test_scan_blocks_against_host_prefix checks the bases
-// of a many-block scan.)  Block b's part (SCAN_TB threads); returns (uniform)
+// (test_gpu_edges.py::test_launch_breakpoints checks the bases of a
+// many-block scan: streams of 1023..2049 tiles.)  Block b's part (SCAN_TB threads); returns (uniform)
 // whether it drew the last ticket.  s_tmp, s_mx: SCAN_TB / 64 words of LDS
 // each, s_last one.
 __device__ __forceinline__ bool fscan_block(const FsmGeo &geo, const FsmWork &wk, uint32_t b, uint32_t nblk, int32_t *s_tmp,

@@ -274,7 +274,9 @@ int hh_decoder_stats(const hh_decoder *dec, hh_stats *st);
  * default stream); the call returns after the output length is known.
  * HH_ERR_CAPACITY (the decode needs more than cap bytes): *out_len is still
  * the stream's full symbol count -- the size to retry with -- here and in
- * hh_decode_host; the output buffer's content is then unspecified.       */
+ * hh_decode_host; the output buffer's content is then unspecified.  On
+ * HH_ERR_CAPACITY, as on success, nothing at or beyond d_out + cap is
+ * written.                                                                */
 int hh_decode_device(hh_decoder *dec, const void *d_data, uint64_t bits,
                      void *d_out, uint64_t cap, uint64_t *out_len,
                      void *hip_stream);

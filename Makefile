@@ -37,7 +37,12 @@ $(BUILD)/hh_plugin.o: $(CSRC)/hh_plugin.c include/hiphuff.h include/hiphuff_plug
 	$(CC) $(CFLAGS) -c $< -o $@
 
 $(BUILD)/hh_device.o: $(CSRC)/hh_device.hip $(CSRC)/hh_algo.h $(CSRC)/hh_internal.h $(CSRC)/hh_fsm_dev.h \
-                      $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h include/hiphuff.h | $(BUILD)
+                      $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_batch.h include/hiphuff.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/hh_batch.o: $(CSRC)/hh_batch.hip $(CSRC)/hh_batch.h $(CSRC)/hh_batch_algo.h $(CSRC)/hh_fsm_kern.h \
+                     $(CSRC)/hh_fsm_dev.h $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_internal.h \
+                     include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/hh_one.o: $(CSRC)/hh_one.hip $(CSRC)/hh_fsm_kern.h $(CSRC)/hh_fsm_dev.h $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h \
@@ -60,7 +65,7 @@ $(BUILD)/hh_build.o: $(CSRC)/hh_build.c include/hiphuff.h | $(BUILD)
 $(BUILD)/hh_probe.o: $(CSRC)/hh_probe.hip include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/hh_device.o $(BUILD)/hh_fsm.o $(BUILD)/hh_one.o $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
+$(LIB): $(BUILD)/hh_device.o $(BUILD)/hh_fsm.o $(BUILD)/hh_one.o $(BUILD)/hh_batch.o $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 $(CLI): $(PKG)/host/hh_cli.c $(LIB) include/hiphuff.h include/hiphuff_plugin.h
@@ -79,8 +84,10 @@ $(BUILD)/ub_hist: tools/ubench/ub_hist.hip $(CSRC)/hh_hist_kern.h | $(BUILD)
 $(BUILD)/ub_fetch: tools/ubench/ub_fetch.hip | $(BUILD)
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $<
 
-$(EMU): tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp $(CSRC)/hh_algo.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_fsm.h $(CSRC)/hh_internal.h $(BUILD)/hh_huff.o
-	$(CXX) -O2 -fPIC -shared $(INC) -Wno-comment -o $@ tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp $(BUILD)/hh_huff.o
+$(EMU): tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp tests/emu/hh_batch_emu.cpp $(CSRC)/hh_algo.h $(CSRC)/hh_fsm_algo.h \
+        $(CSRC)/hh_batch_algo.h $(CSRC)/hh_fsm.h $(CSRC)/hh_internal.h $(BUILD)/hh_huff.o
+	$(CXX) -O2 -fPIC -shared $(INC) -Wno-comment -o $@ tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp \
+	    tests/emu/hh_batch_emu.cpp $(BUILD)/hh_huff.o
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(EMU)
@@ -94,7 +101,8 @@ variant: $(BUILD)/hh_plugin.o $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/h
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_device.hip -o $(BUILD)/hh_device_$(V).o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_fsm.hip -o $(BUILD)/hh_fsm_$(V).o
 	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_one.hip -o $(BUILD)/hh_one_$(V).o
+	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_batch.hip -o $(BUILD)/hh_batch_$(V).o
 	$(CC) $(CFLAGS) $(HIPEXTRA) -c $(CSRC)/hh_huff.c -o $(BUILD)/hh_huff_$(V).o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(BUILD)/libhiphuff_$(V).so $(BUILD)/hh_device_$(V).o \
-	    $(BUILD)/hh_fsm_$(V).o $(BUILD)/hh_one_$(V).o $(BUILD)/hh_huff_$(V).o $^
+	    $(BUILD)/hh_fsm_$(V).o $(BUILD)/hh_one_$(V).o $(BUILD)/hh_batch_$(V).o $(BUILD)/hh_huff_$(V).o $^
 .PHONY: variant

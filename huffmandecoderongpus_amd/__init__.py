@@ -126,6 +126,9 @@ _SIGS = {
     "hh_decode_device_async": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
     "hh_decode_wait": ([C.c_void_p], C.c_int),
+    "hh_decode_batch_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_void_p], C.c_int),
+    "hh_decode_batch_round_tiles": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     "hh_decoder_tile_bits": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hh_decode_device_range": ([C.c_void_p, C.c_void_p, C.POINTER(_Range), C.c_void_p,
                                 C.c_uint64, C.POINTER(_RangeOut), C.c_void_p], C.c_int),
@@ -535,6 +538,41 @@ class Decoder:
         rc = lib().hh_decode_wait(self._h)
         self._pending = []
         _check(rc, "decode_wait")
+
+    def decode_batch(self, data, items, out, stream=None) -> tuple:
+        """hh_decode_batch_device: n independent streams of this decoder's
+        code in one launch.  data, out: torch uint8 CUDA tensors; items: an
+        (n, 4) uint64 array of (data_off, bits, out_off, cap) rows, the
+        fields of hh_batch_item.  Returns (out_len np.uint64[n], status
+        np.int32[n]).  A failing batch raises HipHuffError with the status
+        of its lowest-index failing stream (.status, as every HipHuffError),
+        carrying the two arrays as .out_len and .statuses."""
+        import torch
+        assert data.is_cuda and out.is_cuda and data.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert data.is_contiguous() and out.is_contiguous()
+        items = np.ascontiguousarray(items, np.uint64)
+        if items.ndim != 2 or items.shape[1] != 4:
+            raise ValueError("items: an (n, 4) array of (data_off, bits, out_off, cap)")
+        n = items.shape[0]
+        s = stream if stream is not None else torch.cuda.current_stream(data.device)
+        out_len = np.zeros(n, np.uint64)
+        status = np.zeros(n, np.int32)
+        rc = lib().hh_decode_batch_device(self._h, data.data_ptr(), data.numel(), items.ctypes.data, n,
+                                          out.data_ptr(), out.numel(),
+                                          out_len.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          status.ctypes.data_as(C.POINTER(C.c_int32)), s.cuda_stream)
+        if rc != 0:
+            e = HipHuffError(rc, "decode_batch")
+            e.out_len, e.statuses = out_len, status
+            raise e
+        return out_len, status
+
+    def batch_round_tiles(self) -> int:
+        """hh_decode_batch_round_tiles: tiles per round of a workgroup of the
+        batched decode, for the current tree."""
+        w = C.c_uint32(0)
+        _check(lib().hh_decode_batch_round_tiles(self._h, C.byref(w)), "batch_round_tiles")
+        return int(w.value)
 
     def tile_bits(self) -> int:
         """Bits per tile for the current tree (segments are whole tiles)."""

@@ -1,0 +1,306 @@
+// hh_batch.hip -- the batched decode: n independent streams of one code in a
+// single launch (hh_decode_batch_device).  HIP (gfx950).
+//
+// k_batch: a workgroup of W waves takes streams from the descriptor list
+// (sorted by the host in descending length; workgroup b takes entries b,
+// b + grid, ...: nothing waits on another workgroup) and decodes each in
+// rounds of W tiles -- 64 W regions of S bits, lane = region -- by the rules
+// of hh_batch_algo.h: guess, count, fix rounds, scan, emission, copy-out.
+// The state entering the next round and the output base are carried from
+// round to round, so a stream needs no second kernel and no scan over tiles.
+//
+// LDS (dynamic only, from address 0: hh_fsm_kern.h's rule):
+//   the emission tables et, er, b1, tsym (emf_tab_bytes; the count pass walks
+//   them too: an entry carries the symbol count and the next state, and the
+//   count table would not fit beside them for a byte alphabet)
+//   the round's payload, a row of SW (+ 1 when SW is even) words per region
+//   wx[16] waves' exit states, wt[16] waves' counts, chg[3] fix-round flags
+//   the round's staging: its symbols at their output address mod 16
+//
+// Output edges: neighbouring streams' outputs may share a dword (any out_off,
+// exact capacities) and another workgroup writes the neighbour, so the
+// copy-out stores whole 16-byte blocks only where all 16 bytes are this
+// round's, and single bytes elsewhere: never a byte it does not own.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "hh_batch.h"
+#include "hh_batch_algo.h"
+#include "hh_fsm_kern.h"
+
+#define HB_LDS (160u * 1024u)
+#define HB_UNTOUCHED 0x7fffffff     // a result slot the kernel did not write
+
+struct BatchGeo {
+    uint32_t ns, K, r, S, G, W;
+    uint32_t pay_off, misc_off, stg_off, stg_bytes;   // LDS byte offsets / the staging's size
+    uint32_t n;
+};
+// a stream, in the kernel's order; idx: its index in the caller's list
+struct BatchDesc {
+    uint64_t data_off, bits, out_off, cap, idx;
+};
+struct BatchRes {
+    uint64_t len;
+    int64_t status;
+};
+
+// The emission sink: a step's symbols shifted into the current dword, which
+// is stored to its aligned staging address once its last byte is there (the
+// bytes of earlier runs in it zero); a run that ends inside a dword ORs its
+// bytes in after every run's stores (k_emf's scheme, hh_fsm.hip).
+struct BatchSink {
+    uint8_t *lds;
+    uint32_t wd, sh, a;
+    __device__ __forceinline__ void init(uint8_t *smem, uint32_t oa) {
+        lds = smem;
+        wd = oa & ~3u;
+        sh = (oa & 3u) * 8u;
+        a = 0;
+    }
+    __host__ __device__ __forceinline__ void put(uint64_t e) {
+        const uint32_t lo = (uint32_t)e, u = sh + ((uint32_t)(e >> 32) & 255u);
+        const uint64_t t = (uint64_t)lo << sh;
+        const uint32_t an = (uint32_t)t | a;
+        const bool full = u >= 32u;
+        if (full) *(uint32_t *)(lds + wd) = an;
+        a = full ? (uint32_t)(t >> 32) : an;
+        wd += full ? 4u : 0u;
+        sh = u & 31u;
+    }
+};
+
+__global__ __launch_bounds__(64 * HB_WMAX) void k_batch(const uint8_t *__restrict__ data,
+                                                        const BatchDesc *__restrict__ desc, BatchRes *__restrict__ res,
+                                                        uint8_t *__restrict__ out, FsmTab tab, BatchGeo geo) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const uint32_t ns = geo.ns, K = geo.K, r = geo.r, S = geo.S, G = geo.G, tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t W = geo.W, SW = S / 32u, RW = hb_row_words(S);
+    const uint32_t er_off = (ns << HH_FSM_ET_LG(K)) * 8u;
+    uint32_t *s_b1 = (uint32_t *)(smem + er_off + (r ? (ns << r) * 8u : 0u));
+    uint8_t *s_ts = (uint8_t *)(s_b1 + 2 * ns);
+    lds_fill16(smem, tab.et, er_off);
+    for (uint32_t i = tid; r && i < (ns << r); i += blockDim.x) ((uint64_t *)(smem + er_off))[i] = tab.er[i];
+    for (uint32_t i = tid; i < 2 * ns; i += blockDim.x) s_b1[i] = tab.b1[i];
+    for (uint32_t i = tid; i < ns; i += blockDim.x) s_ts[i] = tab.tsym[i];
+    const hb_view F = {(const uint64_t *)smem, (const uint64_t *)(smem + er_off), s_b1, s_ts, K, r, S};
+    uint32_t *pay = (uint32_t *)(smem + geo.pay_off);
+    uint32_t *wx = (uint32_t *)(smem + geo.misc_off), *wt = wx + HB_WMAX, *chg = wt + HB_WMAX;
+    uint8_t *stg = smem + geo.stg_off;
+    const bool lds0 = lds_base_is_zero(smem);
+    const uint32_t jr = wv * 64u + lane;                  // the lane's region of a round
+    const uint64_t RB = (uint64_t)HB_NR * W * S;          // a round's bits
+
+    for (uint32_t it = blockIdx.x; it < geo.n; it += gridDim.x) {
+        const uint64_t data_off = uni64(desc[it].data_off), bits = uni64(desc[it].bits);
+        const uint64_t out_off = uni64(desc[it].out_off), cap = uni64(desc[it].cap), idx = uni64(desc[it].idx);
+        const uint32_t *g = (const uint32_t *)(data + data_off);
+        const uint64_t nwords = (bits + 31u) / 32u, rounds = (bits + RB - 1u) / RB;
+        uint64_t base = 0;                                // symbols before the round
+        uint32_t carry = 0, fail = lds0 ? 0u : 1u;        // the state entering the round
+        for (uint64_t rd = 0; rd < rounds; rd++) {
+            const uint64_t R0 = rd * RB, R = R0 + (uint64_t)jr * S;
+            // the round's payload: every lane its region's words into its row
+            // (loads past the stream's words give 0, never read as stream bits)
+            const __amdgpu_buffer_rsrc_t rs = fs_rsrc(g, R0 / 32u, nwords);
+            __syncthreads();                              // the round before has read its rows and its staging
+            uint32_t *row = pay + jr * RW;
+#pragma unroll 4
+            for (uint32_t k = 0; k < SW; k++) row[k] = __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(4u * (jr * SW + k)), 0, 0);
+            if (tid == 0) chg[0] = 0;
+            __syncthreads();
+            int whole, at_end;
+            const uint32_t nb = hb_span(R, S, bits, &whole, &at_end);
+            hb_bits b;
+            uint32_t ent = carry, x, n;
+            if (jr > 0) {
+                ent = 0;
+                if (G && nb) {
+                    hb_bits_init(&b, pay + (jr - 1u) * RW, S - G);
+                    ent = hb_guess(&F, &b, G);
+                }
+            }
+            hb_no_sink none;
+            hb_bits_init(&b, row, 0);
+            x = hb_region(&F, &b, nb, whole, at_end, ent, none, &n);
+            // fix rounds: until no lane's entry differs from its predecessor's exit
+            uint32_t c3 = 0, fr = 0;
+            for (;; fr++) {
+                if (lane == 63u) wx[wv] = x;
+                const uint32_t c3n = c3 == 2u ? 0u : c3 + 1u;
+                if (tid == 0) chg[c3n] = 0;
+                __syncthreads();
+                uint32_t pred = shfl_up1(x);
+                if (lane == 0) pred = wv ? wx[wv - 1u] : carry;
+                const int again = hb_fix(jr, nb, pred, &ent);
+                if (again) {
+                    hb_bits_init(&b, row, 0);
+                    x = hb_region(&F, &b, nb, whole, at_end, ent, none, &n);
+                }
+                if (__builtin_amdgcn_ballot_w64(again != 0) != 0 && lane == 0) chg[c3] = 1u;
+                __syncthreads();
+                const uint32_t any = chg[c3];
+                c3 = c3n;
+                if (!any) break;
+                if (fr >= HB_FIX_BOUND(W)) { fail = 1u; break; }   // (cannot happen: hh_batch_algo.h)
+            }
+            const uint32_t carry_next = wx[W - 1u];        // (the last fix round changed nothing: wx is final)
+            // scan
+            const uint32_t incl = (uint32_t)wave_incl_scan((int32_t)n);
+            if (lane == 63u) wt[wv] = incl;
+            __syncthreads();
+            uint32_t woff = 0, tot = 0;
+            for (uint32_t v = 0; v < W; v++) {
+                const uint32_t t = wt[v];
+                woff += v < wv ? t : 0u;
+                tot += t;
+            }
+            const uint32_t L = woff + incl - n;
+            // emission into the staging, at the output's address mod 16
+            uint8_t *gp = out + out_off + base;
+            const uint32_t a0 = (uint32_t)((uintptr_t)gp & 15u);
+            const uint32_t keep = hb_clip(base, tot, cap);
+            if (a0 + tot + 8u > geo.stg_bytes) fail = 1u;       // (the host sized it for the most a round holds)
+            if (!fail && keep) {
+                if (tid == 0) *(uint32_t *)(stg + ((a0 + tot) & ~3u)) = 0u;   // the last, partial dword: ORs only
+                BatchSink sink;
+                sink.init(smem, geo.stg_off + a0 + L);
+                hb_bits_init(&b, row, 0);
+                uint32_t n2;
+                hb_region(&F, &b, nb, whole, at_end, ent, sink, &n2);
+                __syncthreads();
+                if (sink.sh) atomicOr((uint32_t *)(smem + sink.wd), sink.a);
+                __syncthreads();
+                // copy-out: whole 16-B blocks inside [a0, end), bytes at the edges
+                uint8_t *gb = gp - a0;
+                const uint32_t end = a0 + keep, nq = (end + 15u) / 16u;
+                for (uint32_t q = tid; q < nq; q += blockDim.x) {
+                    const uint32_t lo = 16u * q;
+                    if (lo >= a0 && lo + 16u <= end) {
+                        *(u32x4 *)(gb + lo) = *(const u32x4 *)(stg + lo);
+                    } else {
+                        const uint32_t q0 = lo > a0 ? lo : a0, q1 = lo + 16u < end ? lo + 16u : end;
+                        for (uint32_t p = q0; p < q1; p++) gb[p] = stg[p];
+                    }
+                }
+            }
+            base += tot;
+            carry = carry_next;
+        }
+        if (tid == 0) {
+            res[idx].len = base;
+            res[idx].status = fail ? HH_ERR_INTERNAL : base > cap ? HH_ERR_CAPACITY : HH_OK;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------
+void batch_setup(BatchDev *b, const FsmDev *fd, uint32_t G, uint32_t minlen) {
+    b->ok = b->W = b->lds = b->grid_max = 0;
+    b->G = G;
+    b->minlen = minlen;
+    if (!fd->ok) return;
+    const uint32_t tabb = emf_tab_bytes(fd->ns, fd->K, fd->r);
+    b->W = hb_pick_waves(tabb, fd->S, minlen, HB_LDS);
+    if (!b->W || G % fd->K || G > fd->S) return;        // (no room for one tile's round beside the tables)
+    b->lds = hb_lds_bytes(tabb, fd->S, minlen, b->W);
+    b->ok = 1;
+}
+
+void batch_free(BatchDev *b) {
+    if (b->d_ws) (void)hipFree(b->d_ws);
+    if (b->h_ws) (void)hipHostFree(b->h_ws);
+    memset(b, 0, sizeof(*b));
+}
+
+static int batch_ws(BatchDev *b, size_t need) {
+    if (b->d_size >= need) return HH_OK;
+    // (the call is synchronous and a pending asynchronous decode was checked
+    // before it: nothing on the device still uses the old workspace)
+    if (b->d_ws) FS_OK(hipFree(b->d_ws));
+    if (b->h_ws) FS_OK(hipHostFree(b->h_ws));
+    b->d_ws = b->h_ws = nullptr;
+    b->d_size = b->h_size = 0;
+    const size_t sz = need + need / 8;
+    if (hipMalloc(&b->d_ws, sz) != hipSuccess) return HH_ERR_NOMEM;
+    b->d_size = sz;
+    if (hipHostMalloc(&b->h_ws, sz, hipHostMallocDefault) != hipSuccess) {
+        b->h_ws = nullptr;
+        return HH_ERR_NOMEM;
+    }
+    b->h_size = sz;
+    return HH_OK;
+}
+
+int batch_decode(BatchDev *b, const FsmDev *fd, hipEvent_t *ev, const void *d_data, const hh_batch_item *items,
+                 uint64_t n, void *d_out, uint64_t *out_len, int32_t *status, hipStream_t st, float *ms,
+                 uint64_t *lanes) {
+    if (!b->ok) return HH_ERR_UNSUPPORTED;
+    if (n > 0xffffffffull) return HH_ERR_UNSUPPORTED;
+    if (!b->grid_max) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, (const void *)k_batch) != hipSuccess || fa.sharedSizeBytes != 0) return HH_ERR_INTERNAL;
+        int per = 0, ncu = 0, dev = 0;
+        FS_OK(hipGetDevice(&dev));
+        FS_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_batch, (int)(64 * b->W), b->lds));
+        FS_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+        if (per < 1 || ncu < 1) return HH_ERR_UNSUPPORTED;
+        b->grid_max = (uint32_t)(per * ncu);
+    }
+    const size_t dbytes = (size_t)n * sizeof(BatchDesc), rbytes = (size_t)n * sizeof(BatchRes);
+    const int wrc = batch_ws(b, dbytes + rbytes);
+    if (wrc != HH_OK) return wrc;
+    BatchDesc *hd = (BatchDesc *)b->h_ws;
+    BatchRes *hr = (BatchRes *)((uint8_t *)b->h_ws + dbytes);
+    BatchDesc *dd = (BatchDesc *)b->d_ws;
+    BatchRes *dr = (BatchRes *)((uint8_t *)b->d_ws + dbytes);
+    // the longest streams first: the workgroups that take them start at once
+    std::vector<uint32_t> ord((size_t)n);
+    for (uint32_t i = 0; i < (uint32_t)n; i++) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return items[x].bits > items[y].bits; });
+    uint64_t regions = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        const hh_batch_item &s = items[ord[k]];
+        hd[k] = BatchDesc{s.data_off, s.bits, s.out_off, s.cap, ord[k]};
+        regions += (s.bits + fd->S - 1) / fd->S;
+        hr[k].len = 0;
+        hr[k].status = HB_UNTOUCHED;
+    }
+    *lanes = regions;
+    BatchGeo geo;
+    geo.ns = fd->ns; geo.K = fd->K; geo.r = fd->r; geo.S = fd->S; geo.G = b->G; geo.W = b->W;
+    geo.pay_off = emf_tab_bytes(fd->ns, fd->K, fd->r);
+    geo.misc_off = geo.pay_off + hb_pay_bytes(fd->S, b->W);
+    geo.stg_off = (geo.misc_off + hb_misc_bytes() + 15u) & ~15u;
+    geo.stg_bytes = hb_stage_bytes(fd->S, b->minlen, b->W);
+    geo.n = (uint32_t)n;
+    const FsmTab tab = {fd->ct, fd->b1, fd->tsym, fd->et, fd->er};
+    // descriptors and the untouched marks of the results, on the call's stream
+    FS_OK(hipMemcpyAsync(dd, hd, dbytes + rbytes, hipMemcpyHostToDevice, st));
+    const uint32_t grid = n < b->grid_max ? (uint32_t)n : b->grid_max;
+    FS_OK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_batch, dim3(grid), dim3(64 * b->W), b->lds, st, (const uint8_t *)d_data, dd, dr,
+                       (uint8_t *)d_out, tab, geo);
+    FS_OK(hipGetLastError());
+    FS_OK(hipEventRecord(ev[1], st));
+    FS_OK(hipMemcpyAsync(hr, dr, rbytes, hipMemcpyDeviceToHost, st));
+    FS_OK(hipStreamSynchronize(st));
+    *ms = 0;
+    (void)hipEventElapsedTime(ms, ev[0], ev[1]);
+    int rc = HH_OK;
+    for (uint64_t i = 0; i < n; i++) {
+        const int s = hr[i].status == HB_UNTOUCHED ? HH_ERR_INTERNAL : (int)hr[i].status;
+        out_len[i] = hr[i].len;
+        if (status) status[i] = s;
+        if (s != HH_OK && rc == HH_OK) rc = s;
+    }
+    return rc;
+}

@@ -39,6 +39,7 @@
 #include <thread>
 
 #include "hh_algo.h"
+#include "hh_batch.h"
 #include "hh_fsm_algo.h"
 #include "hh_fsm_dev.h"
 #include "hh_internal.h"
@@ -1448,6 +1449,8 @@ struct hh_decoder {
     } apend;
     int async_rc;              // the first failure since the last hh_decode_wait
     uint32_t async_seq;        // asynchronous decodes launched (the result slot alternates)
+    // the batched decode (hh_batch.hip): its launch shape for the current tree, its workspace
+    BatchDev batch;
 };
 
 static int async_check(hh_decoder *d);
@@ -1533,6 +1536,7 @@ extern "C" void hh_decoder_destroy(hh_decoder *d) {
     if (d->stream) hipStreamDestroy(d->stream);
     fsm_free(&d->fsm);
     fsm_ws_free(&d->fsm_ws);
+    batch_free(&d->batch);
     for (uint32_t i = 0; i < d->npipe_ev; i++) hipEventDestroy(d->pipe_ev[i]);
     free(d->pipe_ev);
     if (d->h2d) hipStreamDestroy(d->h2d);
@@ -1660,6 +1664,12 @@ extern "C" int hh_decoder_set_tree(hh_decoder *d, const hh_tree *tree) {
         uint32_t G1 = hh_fsm_pick_head(d->ht, d->S, d->ft->K);
         if (getenv("HH_FSM_HEAD")) G1 = (uint32_t)atoi(getenv("HH_FSM_HEAD")) / d->ft->K * d->ft->K;   // experiments
         if (urc == HH_OK) one_setup(&d->fsm, G1 > d->S ? 0u : G1, avg, (uint32_t)d->ht->minlen);
+    }
+    // the batched decode (hh_batch.hip) walks the emission tables only: its
+    // head on their K-bit steps too
+    {
+        const uint32_t Gb = d->fsm.ok ? hh_fsm_pick_head(d->ht, d->S, d->fsm.K) : 0u;
+        batch_setup(&d->batch, &d->fsm, Gb > d->S ? 0u : Gb, (uint32_t)d->ht->minlen);
     }
     d->have_tree = 1;
     return HH_OK;
@@ -2247,6 +2257,49 @@ extern "C" int hh_decode_wait(hh_decoder *d) {
     const int rc = d->async_rc;
     d->async_rc = HH_OK;
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// The batched decode (hh_batch.hip): the arguments are checked here, before
+// anything is launched or written.
+// ---------------------------------------------------------------------------
+extern "C" int hh_decode_batch_device(hh_decoder *d, const void *d_data, uint64_t data_bytes,
+                                      const hh_batch_item *items, uint64_t n, void *d_out, uint64_t out_bytes,
+                                      uint64_t *out_len, int32_t *status, void *hip_stream) {
+    if (!d) return HH_ERR_ARG;
+    if (n == 0) return HH_OK;
+    if (!items || !out_len || !d_data || !d_out || !d->have_tree) return HH_ERR_ARG;
+    if (((uintptr_t)d_data & 3u) != 0) return HH_ERR_ARG;   // word loads
+    for (uint64_t i = 0; i < n; i++) {
+        const hh_batch_item &s = items[i];
+        if (s.data_off % 4u) return HH_ERR_ARG;
+        if (s.bits) {
+            const uint64_t nb = s.bits / 8u + (s.bits % 8u != 0) + HH_PAYLOAD_PAD;   // (bits / 8 <= 2^61: no overflow)
+            if (s.data_off > data_bytes || nb > data_bytes - s.data_off) return HH_ERR_ARG;
+        }
+        if (s.out_off > out_bytes || s.cap > out_bytes - s.out_off) return HH_ERR_ARG;
+    }
+    if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;
+    HIP_OK(hipSetDevice(d->device));
+    async_check(d);                     // (an asynchronous decode before it: its status is kept for hh_decode_wait)
+    memset(&d->stats, 0, sizeof(d->stats));
+    float ms = 0;
+    uint64_t lanes = 0;
+    const int rc = batch_decode(&d->batch, &d->fsm, d->ev, d_data, items, n, d_out, out_len, status,
+                                (hipStream_t)hip_stream, &ms, &lanes);
+    if (rc == HH_ERR_DEVICE || rc == HH_ERR_NOMEM || rc == HH_ERR_UNSUPPORTED) return rc;   // (nothing decoded)
+    d->stats.ms_total = ms;
+    d->stats.lanes = lanes;
+    for (uint64_t i = 0; i < n; i++) d->stats.out_len += out_len[i];
+    d->stats.state_machine = 3;
+    return rc;
+}
+
+extern "C" int hh_decode_batch_round_tiles(const hh_decoder *d, uint32_t *tiles) {
+    if (!d || !tiles || !d->have_tree) return HH_ERR_ARG;
+    if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;
+    *tiles = d->batch.W;
+    return HH_OK;
 }
 
 extern "C" int hh_decoder_tile_bits(const hh_decoder *d, uint64_t *tile_bits) {

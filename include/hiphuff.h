@@ -16,7 +16,9 @@
  *   hh_decode_*    the hot path                               replaces openclApproach
  *                                                             (openclapproach.c:236-1047) and
  *                                                             fastgpuApproach (fastgpu.cu:140-332)
- *   hh_stage_*     reference-shaped stage kernels             replaces the six kernels of
+ *   hh_decode_batch_*  many streams of one code per launch   (the reference decodes one
+ *                                                             stream per call)
+ *   hh_stage_*   reference-shaped stage kernels             replaces the six kernels of
  *                                                             ReleaseCL/kernels/ *.cl one by one
  *   hipHuffApproach  plugin with the reference's decoder       decodeUtil.h:14-19 function-pointer
  *                    signature (see hiphuff_plugin.h)          type, registered like mainrun.c:480-488
@@ -261,7 +263,8 @@ typedef struct {
                                 by k_fixed (HH_FLAG_NO_FIXED: 0)            */
     int state_machine;       /* the state-machine decode ran: 1 its two
                                 passes (k_cntm, k_fscan1, k_emf), 2 its
-                                single pass (k_one)                         */
+                                single pass (k_one), 3 the batched decode
+                                (k_batch, hh_decode_batch_device)           */
 } hh_stats;
 
 int hh_decoder_stats(const hh_decoder *dec, hh_stats *st);
@@ -302,6 +305,59 @@ int hh_decode_device_async(hh_decoder *dec, const void *d_data, uint64_t bits,
                            void *d_out, uint64_t cap, uint64_t *out_len,
                            void *hip_stream);
 int hh_decode_wait(hh_decoder *dec);
+
+/* ---------------------------------------------------------------------- */
+/* Batched decode: n independent streams of the decoder's code in ONE     */
+/* kernel launch (k_batch), for many small blocks coded with one shared   */
+/* code -- chunked files, records, pages -- where a call per stream costs */
+/* its launches' fixed time n times over.                                 */
+/* ---------------------------------------------------------------------- */
+typedef struct {
+    uint64_t data_off;   /* byte offset of the stream's payload in d_data; a multiple of 4 */
+    uint64_t bits;       /* stream length; 0 is allowed (out_len 0, nothing written)        */
+    uint64_t out_off;    /* byte offset of its output in d_out; any alignment              */
+    uint64_t cap;        /* bytes it may write at out_off                                  */
+} hh_batch_item;
+
+/* Stream i decodes exactly as hh_decode_device(dec, d_data + data_off, bits,
+ * d_out + out_off, cap, ...) would on its own: the same bytes, the same
+ * out_len[i] (findmax + 1, the tail rule included), each stream from the
+ * root.  Capacity is per stream: status[i] = HH_ERR_CAPACITY, out_len[i] the
+ * stream's full symbol count, nothing written at or beyond out_off + cap;
+ * one stream's failure does not disturb the others.  Returns HH_OK if every
+ * stream is HH_OK, else the status of the lowest-index failing stream
+ * (status may be NULL).  items, out_len and status are host arrays of n.
+ * HH_ERR_ARG, before any launch and with nothing written: a data_off that is
+ * no multiple of 4 (or d_data off a 4-byte boundary); for bits > 0,
+ * data_off + ceil(bits/8) + HH_PAYLOAD_PAD > data_bytes; out_off + cap >
+ * out_bytes; no tree set; a null pointer with n > 0.  n == 0 returns HH_OK.
+ * Payloads may overlap or lie back to back at 4-byte boundaries: the next
+ * stream's bytes serve as the readable pad (pad content is ignored).
+ * Output ranges must not overlap -- the caller's duty, not checked; they
+ * may touch at any alignment (a stream's first and last bytes are stored as
+ * bytes, never as part of a wider store that covers a neighbour's).
+ * Trees: every tree the decoder holds state-machine tables for -- at most
+ * 255 internal nodes, any byte-alphabet code, whatever HH_FLAG_* the decoder
+ * was created with -- whose emission tables leave room in the LDS for one
+ * tile's payload and staging (every tree at the default settings); other
+ * trees return HH_ERR_UNSUPPORTED.  Fixed-length codes, codes longer than 32
+ * bits and codes that do not resynchronise decode exactly here itself (the
+ * last slowly: a region per fix round); there is no fallback path.  n < 2^32.
+ * A stream is decoded by one workgroup, round by round: a very large stream
+ * is hh_decode_device's work, which spreads it over the whole GPU.
+ * Enqueued on hip_stream; returns when done.  A pending asynchronous decode
+ * is checked first (its status kept for hh_decode_wait).  hh_stats after a
+ * batch: out_len the sum over the streams, lanes the regions of all of
+ * them, ms_total the launch's device time, state_machine 3. */
+int hh_decode_batch_device(hh_decoder *dec, const void *d_data, uint64_t data_bytes,
+                           const hh_batch_item *items /* host */, uint64_t n,
+                           void *d_out, uint64_t out_bytes,
+                           uint64_t *out_len /* host, n */, int32_t *status /* host, n, may be NULL */,
+                           void *hip_stream);
+/* The tiles (of hh_decoder_tile_bits() bits, 64 regions) a workgroup of the
+ * batched decode takes per round for the current tree: where a stream's
+ * length changes its number of rounds.  HH_ERR_UNSUPPORTED as above. */
+int hh_decode_batch_round_tiles(const hh_decoder *dec, uint32_t *tiles);
 
 /* ---------------------------------------------------------------------- */
 /* Segments (multi-GPU shards).  The stream is cut into tiles of           */

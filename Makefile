@@ -20,6 +20,10 @@ HIPFLAGS := $(HIPEXTRA) -O3 -fPIC -std=c++17 --offload-arch=$(ARCH) -Wall -Wno-u
 LIB      := $(PKG)/libhiphuff.so
 CLI      := $(BUILD)/HuffFramework
 EMU      := tests/emu/libhh_emu.so
+# the decoder's .hip units, listed once for `lib` and `variant`, and the
+# objects a variant takes as built
+DEC_UNITS  := hh_device hh_fsm hh_one hh_batch
+OTHER_OBJS := $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
 
 all: lib cli oracle emu ubench
 
@@ -65,7 +69,9 @@ $(BUILD)/hh_build.o: $(CSRC)/hh_build.c include/hiphuff.h | $(BUILD)
 $(BUILD)/hh_probe.o: $(CSRC)/hh_probe.hip include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(BUILD)/hh_device.o $(BUILD)/hh_fsm.o $(BUILD)/hh_one.o $(BUILD)/hh_batch.o $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
+# (the link order of before the unit list: the library comes out the same)
+$(LIB): $(DEC_UNITS:%=$(BUILD)/%.o) $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o \
+        $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 $(CLI): $(PKG)/host/hh_cli.c $(LIB) include/hiphuff.h include/hiphuff_plugin.h
@@ -96,13 +102,13 @@ clean:
 .PHONY: all lib cli emu oracle ubench clean
 
 # A/B variant of the library: make variant V=name HIPEXTRA="-DHH_X=1"
-# -> build/libhiphuff_<name>.so (tools/ab.sh)
-variant: $(BUILD)/hh_plugin.o $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_build.o $(BUILD)/hh_probe.o
-	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_device.hip -o $(BUILD)/hh_device_$(V).o
-	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_fsm.hip -o $(BUILD)/hh_fsm_$(V).o
-	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_one.hip -o $(BUILD)/hh_one_$(V).o
-	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/hh_batch.hip -o $(BUILD)/hh_batch_$(V).o
-	$(CC) $(CFLAGS) $(HIPEXTRA) -c $(CSRC)/hh_huff.c -o $(BUILD)/hh_huff_$(V).o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(BUILD)/libhiphuff_$(V).so $(BUILD)/hh_device_$(V).o \
-	    $(BUILD)/hh_fsm_$(V).o $(BUILD)/hh_one_$(V).o $(BUILD)/hh_batch_$(V).o $(BUILD)/hh_huff_$(V).o $^
-.PHONY: variant
+# -> build/libhiphuff_<name>.so (tools/mkvar.sh, tools/gpu_ab.sh): the decoder's
+# units and hh_huff.c compiled again with HIPEXTRA, the rest as built
+$(BUILD)/%_$(V).o: $(CSRC)/%.hip FORCE | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(BUILD)/hh_huff_$(V).o: $(CSRC)/hh_huff.c FORCE | $(BUILD)
+	$(CC) $(CFLAGS) $(HIPEXTRA) -c $< -o $@
+variant: $(DEC_UNITS:%=$(BUILD)/%_$(V).o) $(BUILD)/hh_huff_$(V).o $(OTHER_OBJS)
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(BUILD)/libhiphuff_$(V).so $^
+FORCE:
+.PHONY: variant FORCE

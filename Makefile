@@ -23,7 +23,8 @@ EMU      := tests/emu/libhh_emu.so
 # the decoder's .hip units, listed once for `lib` and `variant`, and the
 # objects a variant takes as built
 DEC_UNITS  := hh_device hh_fsm hh_one hh_batch
-OTHER_OBJS := $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
+OTHER_OBJS := $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_build.o \
+              $(BUILD)/hh_plugin.o
 
 all: lib cli oracle emu ubench
 
@@ -57,7 +58,12 @@ $(BUILD)/hh_fsm.o: $(CSRC)/hh_fsm.hip $(CSRC)/hh_fsm_kern.h $(CSRC)/hh_fsm_dev.h
                    $(CSRC)/hh_internal.h include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/hh_encode.o: $(CSRC)/hh_encode.hip $(CSRC)/hh_internal.h $(CSRC)/hh_enc.h include/hiphuff.h | $(BUILD)
+$(BUILD)/hh_encode.o: $(CSRC)/hh_encode.hip $(CSRC)/hh_enc_kern.h $(CSRC)/hh_internal.h $(CSRC)/hh_enc.h \
+                      include/hiphuff.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/hh_encb.o: $(CSRC)/hh_encb.hip $(CSRC)/hh_enc_kern.h $(CSRC)/hh_internal.h $(CSRC)/hh_enc.h \
+                    include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/hh_hist.o: $(CSRC)/hh_hist.hip $(CSRC)/hh_hist_kern.h $(CSRC)/hh_enc.h include/hiphuff.h | $(BUILD)
@@ -70,8 +76,8 @@ $(BUILD)/hh_probe.o: $(CSRC)/hh_probe.hip include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # (the link order of before the unit list: the library comes out the same)
-$(LIB): $(DEC_UNITS:%=$(BUILD)/%.o) $(BUILD)/hh_encode.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o \
-        $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
+$(LIB): $(DEC_UNITS:%=$(BUILD)/%.o) $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o \
+        $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 $(CLI): $(PKG)/host/hh_cli.c $(LIB) include/hiphuff.h include/hiphuff_plugin.h

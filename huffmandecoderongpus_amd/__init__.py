@@ -117,6 +117,14 @@ _SIGS = {
     "hh_compress_bound": ([C.c_uint64], C.c_uint64),
     "hh_compress_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_TreeBuf),
                             C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
+    "hh_encode_blocks_bound": ([C.POINTER(_Tree), C.c_uint64, C.c_uint64], C.c_uint64),
+    "hh_encode_blocks": ([C.POINTER(_Tree), C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                          C.POINTER(C.c_uint64)], C.c_int),
+    "hh_encoder_encode_blocks": ([C.c_void_p, C.POINTER(_Tree), C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                  C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
+    "hh_compress_blocks_bound": ([C.c_uint64, C.c_uint64], C.c_uint64),
+    "hh_compress_blocks_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.POINTER(_TreeBuf), C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
     "hh_decoder_create": ([C.POINTER(C.c_void_p), C.POINTER(_Config)], C.c_int),
     "hh_decoder_destroy": ([C.c_void_p], None),
     "hh_decoder_set_tree": ([C.c_void_p, C.POINTER(_Tree)], C.c_int),
@@ -300,6 +308,48 @@ class Tree:
         nb = (bits.value + 7) // 8
         return out[: nb + PAYLOAD_PAD].copy(), int(bits.value)
 
+    def encode_blocks(self, syms: np.ndarray, block_syms: int, cap: Optional[int] = None) -> tuple:
+        """The host reference of the blocked encode (hh_encode_blocks): syms
+        cut into blocks of block_syms, each encoded on its own and packed at
+        4-byte boundaries -> (data + PAYLOAD_PAD zero bytes, items (nb, 4)
+        uint64: data_off, bits, out_off, cap -- what Decoder.decode_batch
+        takes).  cap: the output's capacity (default: encode_blocks_bound); a
+        HipHuffError of status -5 carries .items and .total_bytes."""
+        syms = np.ascontiguousarray(syms, np.uint8)
+        n = len(syms)
+        if cap is None:
+            cap = encode_blocks_bound(self, n, block_syms) if block_syms > 0 else 0
+        out = np.zeros(cap + PAYLOAD_PAD, np.uint8)
+        items = np.zeros((_nblocks(n, block_syms), 4), np.uint64)
+        total = C.c_uint64(0)
+        rc = lib().hh_encode_blocks(C.byref(self._c), syms.ctypes.data, n, block_syms, out.ctypes.data, cap,
+                                    items.ctypes.data, C.byref(total))
+        if rc == -5:
+            e = HipHuffError(rc, "encode_blocks")
+            e.items, e.total_bytes = items, int(total.value)
+            raise e
+        _check(rc, "encode_blocks")
+        return out[: total.value + PAYLOAD_PAD].copy(), items
+
+
+def _nblocks(n: int, block_syms: int) -> int:
+    return -(-n // block_syms) if block_syms > 0 else 0
+
+
+def encode_blocks_bound(tree: "Tree", n: int, block_syms: int) -> int:
+    """hh_encode_blocks_bound: bytes that always hold the blocked stream of n
+    symbols of tree."""
+    bound = int(lib().hh_encode_blocks_bound(C.byref(tree._c), n, block_syms))
+    if bound == 0 and n:
+        raise HipHuffError(-4 if block_syms > 0 else -1, "encode_blocks bound")
+    return bound
+
+
+def compress_blocks_bound(n: int, block_syms: int) -> int:
+    """hh_compress_blocks_bound: bytes that always hold n symbols compressed
+    in blocks of block_syms with their own Huffman code."""
+    return int(lib().hh_compress_blocks_bound(n, block_syms))
+
 
 def encode_device(tree: "Tree", syms, out, stream=None) -> int:
     """Pack torch uint8 CUDA symbols with tree's codes into the torch uint8
@@ -364,6 +414,56 @@ class Encoder:
             raise e
         _check(rc, "compress")
         return Tree._from_buf(tb), int(bits.value)
+
+    def encode_blocks(self, tree: "Tree", syms, block_syms: int, out, stream=None) -> tuple:
+        """hh_encoder_encode_blocks: syms cut into blocks of block_syms, every
+        block its own stream from the root, packed into out at 4-byte
+        boundaries in one call (syms, out: torch uint8 CUDA tensors; out
+        holds encode_blocks_bound(tree, n, block_syms) bytes, plus PAYLOAD_PAD
+        for a decode).  Returns (items, total_bytes): items an (nb, 4) uint64
+        array of (data_off, bits, out_off, cap) rows that goes straight into
+        Decoder.decode_batch(out, items, dst).  A HipHuffError of status -5
+        (capacity) carries .items and .total_bytes."""
+        import torch
+        assert syms.is_cuda and out.is_cuda and syms.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert syms.is_contiguous() and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(syms.device)
+        n = syms.numel()
+        items = np.zeros((_nblocks(n, block_syms), 4), np.uint64)
+        total = C.c_uint64(0)
+        rc = lib().hh_encoder_encode_blocks(self._h, C.byref(tree._c), syms.data_ptr() if n else None, n, block_syms,
+                                            out.data_ptr(), out.numel(), items.ctypes.data, C.byref(total),
+                                            s.cuda_stream)
+        if rc == -5:
+            e = HipHuffError(rc, "encoder_encode_blocks")
+            e.items, e.total_bytes = items, int(total.value)
+            raise e
+        _check(rc, "encoder_encode_blocks")
+        return items, int(total.value)
+
+    def compress_blocks(self, syms, block_syms: int, out, stream=None) -> tuple:
+        """hh_compress_blocks_device: histogram, one tree for all blocks, then
+        encode_blocks with it (out holds compress_blocks_bound(n, block_syms)
+        bytes, plus PAYLOAD_PAD for a decode).  Returns (Tree, items,
+        total_bytes).  A HipHuffError of status -5 (capacity) carries .tree,
+        .items and .total_bytes."""
+        import torch
+        assert syms.is_cuda and out.is_cuda and syms.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert syms.is_contiguous() and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(syms.device)
+        n = syms.numel()
+        tb = _TreeBuf()
+        items = np.zeros((_nblocks(n, block_syms), 4), np.uint64)
+        total = C.c_uint64(0)
+        rc = lib().hh_compress_blocks_device(self._h, syms.data_ptr() if n else None, n, block_syms, out.data_ptr(),
+                                             out.numel(), C.byref(tb), items.ctypes.data, C.byref(total),
+                                             s.cuda_stream)
+        if rc == -5:
+            e = HipHuffError(rc, "compress_blocks")
+            e.tree, e.items, e.total_bytes = Tree._from_buf(tb), items, int(total.value)
+            raise e
+        _check(rc, "compress_blocks")
+        return Tree._from_buf(tb), items, int(total.value)
 
     def close(self):
         if self._h:

@@ -1,5 +1,6 @@
 // hh_enc.h -- the encoder handle, shared by csrc/hh_encode.hip (encode,
-// compress) and csrc/hh_hist.hip (histogram).  Not part of the public ABI.
+// compress), csrc/hh_encb.hip (blocked encode, compress) and csrc/hh_hist.hip
+// (histogram).  Not part of the public ABI.
 #ifndef HH_ENC_H_
 #define HH_ENC_H_
 
@@ -19,6 +20,8 @@ struct hh_encoder {
     uint8_t *hist_ws;       // [rows][256] u32 slab, then 256 u64 counts
     size_t hist_size;
     int cus;                // compute units of the device (0: not asked yet)
+    uint64_t *host_bits;    // page-locked: a blocked encode's per-block bits come back here
+    size_t host_bits_n;     // (entries)
 };
 
 #endif

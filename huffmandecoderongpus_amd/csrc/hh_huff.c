@@ -246,20 +246,15 @@ uint64_t hh_encode_bound(const hh_tree *t, uint64_t n) {
     return (n * (uint64_t)in.maxlen + 7) / 8 + 16;
 }
 
-int hh_encode(const hh_tree *t, const uint8_t *syms, uint64_t n, uint8_t *out,
-              uint64_t *bits) {
-    if (!t || (!syms && n) || !out || !bits) return HH_ERR_ARG;
-    codebook cb;
-    int rc = build_codebook(t, &cb);
-    if (rc) return rc;
+/* n symbols packed from out[0]; returns the bits (every symbol is in cb) */
+static uint64_t encode_with(const codebook *cb, const uint8_t *syms, uint64_t n, uint8_t *out) {
     uint64_t acc = 0, pos = 0;   /* acc holds `fill` pending bits */
     unsigned fill = 0;
     uint64_t ob = 0;
     for (uint64_t i = 0; i < n; i++) {
         uint8_t s = syms[i];
-        if (!cb.have[s]) return HH_ERR_ARG;
-        uint64_t c = cb.code[s];
-        unsigned l = cb.len[s];
+        uint64_t c = cb->code[s];
+        unsigned l = cb->len[s];
         /* split codes so the accumulator never overflows */
         while (l) {
             unsigned take = l < 32 ? l : 32;
@@ -276,7 +271,61 @@ int hh_encode(const hh_tree *t, const uint8_t *syms, uint64_t n, uint8_t *out,
         }
     }
     if (fill) out[ob++] = (uint8_t)acc;
-    *bits = pos;
+    return pos;
+}
+
+int hh_encode(const hh_tree *t, const uint8_t *syms, uint64_t n, uint8_t *out,
+              uint64_t *bits) {
+    if (!t || (!syms && n) || !out || !bits) return HH_ERR_ARG;
+    codebook cb;
+    int rc = build_codebook(t, &cb);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < n; i++)
+        if (!cb.have[syms[i]]) return HH_ERR_ARG;
+    *bits = encode_with(&cb, syms, n, out);
+    return HH_OK;
+}
+
+/* Blocked encode on the host (the device form: csrc/hh_encb.hip). */
+uint64_t hh_encode_blocks_bound(const hh_tree *t, uint64_t n, uint64_t block_syms) {
+    hh_tree_info in;
+    if (!block_syms || hh_tree_check(t, &in)) return 0;
+    const uint64_t rest = n % block_syms;
+    return n / block_syms * (((block_syms * (uint64_t)in.maxlen + 7) / 8 + 3) / 4 * 4)
+           + ((rest * (uint64_t)in.maxlen + 7) / 8 + 3) / 4 * 4;
+}
+
+int hh_encode_blocks(const hh_tree *t, const uint8_t *syms, uint64_t n, uint64_t block_syms,
+                     uint8_t *out, uint64_t cap, hh_batch_item *items, uint64_t *total_bytes) {
+    if (!t || !total_bytes || block_syms == 0 || (n && (!syms || !items)) || (!out && cap)) return HH_ERR_ARG;
+    *total_bytes = 0;
+    codebook cb;
+    int rc = build_codebook(t, &cb);
+    if (rc) return rc;
+    /* the lengths first: the items, the total, the capacity check */
+    const uint64_t nb = n / block_syms + (n % block_syms != 0);
+    uint64_t off = 0;
+    for (uint64_t b = 0; b < nb; b++) {
+        const uint64_t s0 = b * block_syms, len = n - s0 < block_syms ? n - s0 : block_syms;
+        uint64_t bits = 0;
+        for (uint64_t i = 0; i < len; i++) {
+            if (!cb.have[syms[s0 + i]]) return HH_ERR_ARG;
+            bits += cb.len[syms[s0 + i]];
+        }
+        items[b].data_off = off;
+        items[b].bits = bits;
+        items[b].out_off = s0;
+        items[b].cap = len;
+        off += (bits + 31) / 32 * 4;
+    }
+    *total_bytes = off;
+    if (off > cap) return HH_ERR_CAPACITY;
+    for (uint64_t b = 0; b < nb; b++) {
+        const uint64_t end = b + 1 < nb ? items[b + 1].data_off : off;
+        uint64_t at = items[b].data_off + (encode_with(&cb, syms + items[b].out_off, items[b].cap,
+                                                       out + items[b].data_off) + 7) / 8;
+        while (at < end) out[at++] = 0;          /* up to the next block's word */
+    }
     return HH_OK;
 }
 

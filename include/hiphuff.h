@@ -18,6 +18,8 @@
  *                                                             fastgpuApproach (fastgpu.cu:140-332)
  *   hh_decode_batch_*  many streams of one code per launch   (the reference decodes one
  *                                                             stream per call)
+ *   hh_encode_blocks*, hh_encoder_encode_blocks, hh_compress_blocks_*
+ *                  the batch's producer: blocks of one text, each its own stream
  *   hh_stage_*   reference-shaped stage kernels             replaces the six kernels of
  *                                                             ReleaseCL/kernels/ *.cl one by one
  *   hipHuffApproach  plugin with the reference's decoder       decodeUtil.h:14-19 function-pointer
@@ -358,6 +360,64 @@ int hh_decode_batch_device(hh_decoder *dec, const void *d_data, uint64_t data_by
  * batched decode takes per round for the current tree: where a stream's
  * length changes its number of rounds.  HH_ERR_UNSUPPORTED as above. */
 int hh_decode_batch_round_tiles(const hh_decoder *dec, uint32_t *tiles);
+
+/* ---------------------------------------------------------------------- */
+/* Blocked encode: the producer of a batch.  n symbols are cut into       */
+/* nb = ceil(n / block_syms) blocks, block b the symbols                  */
+/* [b * block_syms, min(n, (b + 1) * block_syms)), and every block is     */
+/* encoded on its own from the root, exactly as hh_encode would encode    */
+/* those symbols alone -- all of them in one call (one set of launches).  */
+/* ---------------------------------------------------------------------- */
+/* Layout: block b starts at byte data_off[b] of the output, data_off[0] = 0,
+ * data_off[b + 1] = data_off[b] + ceil(bits[b] / 32) * 4 (every block starts
+ * on a 4-byte boundary), *total_bytes = data_off[nb]; the bits between a
+ * block's last bit and the next 4-byte boundary are zero.  items (host, nb
+ * entries) receives items[b] = {data_off[b], bits[b], out_off = b *
+ * block_syms, cap = the symbols in block b}: the array passes unchanged to
+ * hh_decode_batch_device, which gives the symbols back in place.  For that
+ * decode the caller allocates *total_bytes + HH_PAYLOAD_PAD bytes for d_out
+ * (the last block's readable pad; its content is ignored).
+ * hh_encode_blocks_bound: bytes that always hold the blocked stream of n
+ * symbols of tree -- per block ceil(len_b * maxlen / 8) rounded up to 4,
+ * summed; 0 for a bad tree (as hh_encode_bound) or block_syms == 0.
+ * hh_encode_blocks: the host reference, the same bytes and items as the
+ * device call (out: cap bytes, any alignment).
+ * hh_encoder_encode_blocks: on the GPU through an encoder (its workspace,
+ * grown on demand), d_syms and d_out device pointers, d_out 4-byte aligned.
+ * Enqueued on hip_stream, returns when done, as hh_encoder_encode; one call
+ * at a time per encoder; no device-wide wait, nothing on the null stream.
+ * Nothing is written at or beyond d_out + *total_bytes.
+ * HH_ERR_ARG: block_syms == 0, a null pointer with n > 0, d_out off a 4-byte
+ * boundary, a symbol absent from the tree in any block.  HH_ERR_CAPACITY:
+ * *total_bytes > cap, found after the length pass and before any byte of the
+ * output is written; items and *total_bytes are filled (the size to retry
+ * with).  HH_ERR_UNSUPPORTED (device call): nb >= 2^32, more pieces than a
+ * launch's grid holds (nb * ceil(block_syms / 4096) above about 2^24), codes
+ * over 64 bits.  n == 0: HH_OK, *total_bytes = 0, nothing written. */
+uint64_t hh_encode_blocks_bound(const hh_tree *tree, uint64_t n, uint64_t block_syms);
+int hh_encode_blocks(const hh_tree *tree, const uint8_t *syms, uint64_t n, uint64_t block_syms,
+                     uint8_t *out, uint64_t cap, hh_batch_item *items, uint64_t *total_bytes);
+int hh_encoder_encode_blocks(hh_encoder *enc, const hh_tree *tree, const void *d_syms, uint64_t n,
+                             uint64_t block_syms, void *d_out, uint64_t cap,
+                             hh_batch_item *items /* host, nb */, uint64_t *total_bytes,
+                             void *hip_stream);
+/* Compress into blocks: the histogram of all n > 0 bytes, hh_tree_build, then
+ * hh_encoder_encode_blocks with that one tree, which *tree receives (also
+ * with HH_ERR_CAPACITY).  The blocks' bits must add up to the histogram's
+ * sum of count x code length, else HH_ERR_INTERNAL.  n == 0: HH_ERR_ARG, as
+ * hh_compress_device.
+ * hh_compress_blocks_bound(n, block_syms) = (n + 3) / 4 * 4 + 4 * nb always
+ * suffices: the code is shared by all blocks, so a single block of rare
+ * symbols may cost more than 8 bits per symbol, but the total is at most 8 n
+ * bits (hh_compress_bound's argument: a Huffman code over bytes never exceeds
+ * 8 bits per symbol on average over its own text), and rounding a block up to
+ * a whole 32-bit word adds less than 4 bytes per block.  0 for block_syms ==
+ * 0.  Add HH_PAYLOAD_PAD bytes to decode d_out in place. */
+uint64_t hh_compress_blocks_bound(uint64_t n, uint64_t block_syms);
+int hh_compress_blocks_device(hh_encoder *enc, const void *d_syms, uint64_t n, uint64_t block_syms,
+                              void *d_out, uint64_t cap, hh_tree_buf *tree,
+                              hh_batch_item *items /* host, nb */, uint64_t *total_bytes,
+                              void *hip_stream);
 
 /* ---------------------------------------------------------------------- */
 /* Segments (multi-GPU shards).  The stream is cut into tiles of           */

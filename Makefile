@@ -22,7 +22,9 @@ CLI      := $(BUILD)/HuffFramework
 EMU      := tests/emu/libhh_emu.so
 # the decoder's .hip units, listed once for `lib` and `variant`, and the
 # objects a variant takes as built
-DEC_UNITS  := hh_device hh_fsm hh_one hh_batch
+DEC_UNITS  := hh_device hh_r2 hh_exact hh_host hh_fsm hh_one hh_batch
+DEC_HDRS   := $(addprefix $(CSRC)/,hh_algo.h hh_batch.h hh_batch_algo.h hh_dec.h hh_fsm.h hh_fsm_algo.h hh_fsm_dev.h \
+              hh_fsm_kern.h hh_internal.h) include/hiphuff.h
 OTHER_OBJS := $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_build.o \
               $(BUILD)/hh_plugin.o
 
@@ -41,21 +43,9 @@ $(BUILD)/hh_huff.o: $(CSRC)/hh_huff.c $(CSRC)/hh_internal.h $(CSRC)/hh_fsm.h inc
 $(BUILD)/hh_plugin.o: $(CSRC)/hh_plugin.c include/hiphuff.h include/hiphuff_plugin.h | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(BUILD)/hh_device.o: $(CSRC)/hh_device.hip $(CSRC)/hh_algo.h $(CSRC)/hh_internal.h $(CSRC)/hh_fsm_dev.h \
-                      $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_batch.h include/hiphuff.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/hh_batch.o: $(CSRC)/hh_batch.hip $(CSRC)/hh_batch.h $(CSRC)/hh_batch_algo.h $(CSRC)/hh_fsm_kern.h \
-                     $(CSRC)/hh_fsm_dev.h $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_internal.h \
-                     include/hiphuff.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/hh_one.o: $(CSRC)/hh_one.hip $(CSRC)/hh_fsm_kern.h $(CSRC)/hh_fsm_dev.h $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h \
-                   $(CSRC)/hh_internal.h include/hiphuff.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/hh_fsm.o: $(CSRC)/hh_fsm.hip $(CSRC)/hh_fsm_kern.h $(CSRC)/hh_fsm_dev.h $(CSRC)/hh_fsm.h $(CSRC)/hh_fsm_algo.h \
-                   $(CSRC)/hh_internal.h include/hiphuff.h | $(BUILD)
+# the decoder's units: one rule, every private header a prerequisite of each
+# (a unit rebuilt once too often rather than once too seldom)
+$(DEC_UNITS:%=$(BUILD)/%.o): $(BUILD)/%.o: $(CSRC)/%.hip $(DEC_HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/hh_encode.o: $(CSRC)/hh_encode.hip $(CSRC)/hh_enc_kern.h $(CSRC)/hh_internal.h $(CSRC)/hh_enc.h \
@@ -75,7 +65,6 @@ $(BUILD)/hh_build.o: $(CSRC)/hh_build.c include/hiphuff.h | $(BUILD)
 $(BUILD)/hh_probe.o: $(CSRC)/hh_probe.hip include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# (the link order of before the unit list: the library comes out the same)
 $(LIB): $(DEC_UNITS:%=$(BUILD)/%.o) $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o \
         $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^

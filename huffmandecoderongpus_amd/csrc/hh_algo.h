@@ -1,8 +1,8 @@
 /*
  * hh_algo.h -- per-lane building blocks of the O(N) speculative decoder.
  *
- * Everything here is __host__ __device__: the HIP kernel (hh_device.hip)
- * calls it on LDS-resident data, and the test-only emulator
+ * Everything here is __host__ __device__: the HIP kernels (hh_r2.hip, and
+ * hh_exact.hip's segment path) call it on LDS-resident data, and the test-only emulator
  * (tests/emu/hh_emu.cpp) calls it on host arrays with the kernel's exact
  * tile geometry and LDS layout, so the stitching logic is checked against
  * the oracle without a GPU.

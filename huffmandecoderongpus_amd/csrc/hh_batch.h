@@ -1,6 +1,6 @@
 // hh_batch.h -- host interface of the batched decode (hh_batch.hip), used by
-// the decoder's host side (hh_device.hip).  C++ only, not part of the public
-// ABI.
+// the decoder's entry points (hh_device.hip; BatchDev is part of struct
+// hh_decoder, hh_dec.h).  C++ only, not part of the public ABI.
 #ifndef HH_BATCH_H_
 #define HH_BATCH_H_
 

@@ -1649,8 +1649,8 @@ int fsm_launch(FsmDev *fd, FsmWs *ws, uint32_t slot, hipEvent_t *ev, const void 
     FS_OK(hipGetLastError());
     if (fd->phases) FS_OK(hipEventRecord(ev[2], st));
     if (emit_from < nt) {
-        const uint32_t ew = emf_waves(), ew1 = emf_waves();
-        const uint32_t ntb = (uint32_t)((nt - ne + ew1 - 1) / ew1);
+        const uint32_t ew = emf_waves();
+        const uint32_t ntb = (uint32_t)((nt - ne + ew - 1) / ew);
         if (ne > emit_from) {
             const uint64_t nwg = (ne - emit_from + ew - 1) / ew;
             const uint32_t gm = fd->grid_e > ntb + 1 ? fd->grid_e - ntb : 1u;
@@ -1660,7 +1660,7 @@ int fsm_launch(FsmDev *fd, FsmWs *ws, uint32_t slot, hipEvent_t *ev, const void 
                                (uint32_t)lds_emf(fd), ne, nt, ntb);
             FS_OK(hipGetLastError());
         } else if (ne < nt) {
-            hipLaunchKernelGGL(kemf_for(sw, fd->K, true, false), dim3(ntb), dim3(64 * ew1), lds_emf(fd), st,
+            hipLaunchKernelGGL(kemf_for(sw, fd->K, true, false), dim3(ntb), dim3(64 * ew), lds_emf(fd), st,
                                (const uint32_t *)d_data, geo, tab, wk, (uint8_t *)d_out, cap, ne, nt,
                                (uint32_t)lds_emf(fd), (uint64_t)0, (uint64_t)0, 0u);
             FS_OK(hipGetLastError());
@@ -1704,10 +1704,9 @@ int fsm_collect(FsmWs *ws, hipEvent_t *ev, const FsmPend *pd, uint64_t *total, u
     return HH_OK;
 }
 
-int fsm_decode(FsmDev *fd, FsmWs *ws, uint32_t *h_flags, hipEvent_t *ev, const void *d_data, uint64_t bits,
+int fsm_decode(FsmDev *fd, FsmWs *ws, hipEvent_t *ev, const void *d_data, uint64_t bits,
                uint64_t ntiles, uint32_t in_state, uint64_t emit_from, void *d_out, uint64_t cap,
                hipStream_t st, uint64_t *total, uint32_t *leave, uint32_t *entry, float *ms) {
-    (void)h_flags;
     FsmPend pd;
     int rc = fsm_launch(fd, ws, 0, ev, d_data, bits, ntiles, in_state, emit_from, d_out, cap, st, &pd);
     if (rc) return rc;

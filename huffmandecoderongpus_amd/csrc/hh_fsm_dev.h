@@ -1,5 +1,5 @@
 // hh_fsm_dev.h -- host interface of the state-machine decode kernels
-// (hh_fsm.hip), used by the decoder's host side (hh_device.hip).  C++ only,
+// (hh_fsm.hip), used by the decoder's host side (hh_device.hip, hh_host.hip).  C++ only,
 // not part of the public ABI.
 #ifndef HH_FSM_DEV_H_
 #define HH_FSM_DEV_H_
@@ -74,7 +74,7 @@ struct FsmPend {
 // more fix rounds than it allows): decode it again with the two passes
 #define HH_ONE_RETRY (-101)
 void fsm_ws_free(FsmWs *ws);
-int fsm_decode(FsmDev *fd, FsmWs *ws, uint32_t *h_flags, hipEvent_t *ev, const void *d_data, uint64_t bits,
+int fsm_decode(FsmDev *fd, FsmWs *ws, hipEvent_t *ev, const void *d_data, uint64_t bits,
                uint64_t ntiles, uint32_t in_state, uint64_t emit_from, void *d_out, uint64_t cap,
                hipStream_t st, uint64_t *total, uint32_t *leave, uint32_t *entry, float *ms);
 // fsm_decode in two halves: fsm_launch enqueues the decode (results into

@@ -125,6 +125,12 @@ _SIGS = {
     "hh_compress_blocks_bound": ([C.c_uint64, C.c_uint64], C.c_uint64),
     "hh_compress_blocks_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                    C.POINTER(_TreeBuf), C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p], C.c_int),
+    "hh_encoder_encode_blocks_items": ([C.c_void_p, C.POINTER(_Tree), C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p],
+                                       C.c_int),
+    "hh_compress_blocks_device_items": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                         C.POINTER(_TreeBuf), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                         C.c_void_p], C.c_int),
     "hh_decoder_create": ([C.POINTER(C.c_void_p), C.POINTER(_Config)], C.c_int),
     "hh_decoder_destroy": ([C.c_void_p], None),
     "hh_decoder_set_tree": ([C.c_void_p, C.POINTER(_Tree)], C.c_int),
@@ -136,6 +142,8 @@ _SIGS = {
     "hh_decode_wait": ([C.c_void_p], C.c_int),
     "hh_decode_batch_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_void_p], C.c_int),
+    "hh_decode_batch_device_items": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                      C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hh_decode_batch_round_tiles": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     "hh_decoder_tile_bits": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hh_decode_device_range": ([C.c_void_p, C.c_void_p, C.POINTER(_Range), C.c_void_p,
@@ -415,7 +423,17 @@ class Encoder:
         _check(rc, "compress")
         return Tree._from_buf(tb), int(bits.value)
 
-    def encode_blocks(self, tree: "Tree", syms, block_syms: int, out, stream=None) -> tuple:
+    @staticmethod
+    def _items_out_ptr(items_out, nb: int):
+        """The device pointer of items_out, an int64 (nb, 4) CUDA tensor that
+        receives the items for Decoder.decode_batch_items."""
+        import torch
+        if not (items_out.is_cuda and items_out.dtype == torch.int64 and items_out.is_contiguous()
+                and tuple(items_out.shape) == (nb, 4)):
+            raise ValueError(f"items_out: a contiguous CUDA int64 tensor of shape ({nb}, 4)")
+        return items_out.data_ptr() if nb else None
+
+    def encode_blocks(self, tree: "Tree", syms, block_syms: int, out, stream=None, items_out=None) -> tuple:
         """hh_encoder_encode_blocks: syms cut into blocks of block_syms, every
         block its own stream from the root, packed into out at 4-byte
         boundaries in one call (syms, out: torch uint8 CUDA tensors; out
@@ -423,7 +441,9 @@ class Encoder:
         for a decode).  Returns (items, total_bytes): items an (nb, 4) uint64
         array of (data_off, bits, out_off, cap) rows that goes straight into
         Decoder.decode_batch(out, items, dst).  A HipHuffError of status -5
-        (capacity) carries .items and .total_bytes."""
+        (capacity) carries .items and .total_bytes.  items_out: an int64
+        (nb, 4) CUDA tensor that receives the same rows on the device
+        (hh_encoder_encode_blocks_items), for Decoder.decode_batch_items."""
         import torch
         assert syms.is_cuda and out.is_cuda and syms.dtype == torch.uint8 and out.dtype == torch.uint8
         assert syms.is_contiguous() and out.is_contiguous()
@@ -431,9 +451,15 @@ class Encoder:
         n = syms.numel()
         items = np.zeros((_nblocks(n, block_syms), 4), np.uint64)
         total = C.c_uint64(0)
-        rc = lib().hh_encoder_encode_blocks(self._h, C.byref(tree._c), syms.data_ptr() if n else None, n, block_syms,
-                                            out.data_ptr(), out.numel(), items.ctypes.data, C.byref(total),
-                                            s.cuda_stream)
+        if items_out is not None:
+            rc = lib().hh_encoder_encode_blocks_items(self._h, C.byref(tree._c), syms.data_ptr() if n else None, n,
+                                                      block_syms, out.data_ptr(), out.numel(),
+                                                      self._items_out_ptr(items_out, items.shape[0]),
+                                                      items.ctypes.data, C.byref(total), s.cuda_stream)
+        else:
+            rc = lib().hh_encoder_encode_blocks(self._h, C.byref(tree._c), syms.data_ptr() if n else None, n,
+                                                block_syms, out.data_ptr(), out.numel(), items.ctypes.data,
+                                                C.byref(total), s.cuda_stream)
         if rc == -5:
             e = HipHuffError(rc, "encoder_encode_blocks")
             e.items, e.total_bytes = items, int(total.value)
@@ -441,12 +467,13 @@ class Encoder:
         _check(rc, "encoder_encode_blocks")
         return items, int(total.value)
 
-    def compress_blocks(self, syms, block_syms: int, out, stream=None) -> tuple:
+    def compress_blocks(self, syms, block_syms: int, out, stream=None, items_out=None) -> tuple:
         """hh_compress_blocks_device: histogram, one tree for all blocks, then
         encode_blocks with it (out holds compress_blocks_bound(n, block_syms)
         bytes, plus PAYLOAD_PAD for a decode).  Returns (Tree, items,
         total_bytes).  A HipHuffError of status -5 (capacity) carries .tree,
-        .items and .total_bytes."""
+        .items and .total_bytes.  items_out: as in encode_blocks
+        (hh_compress_blocks_device_items)."""
         import torch
         assert syms.is_cuda and out.is_cuda and syms.dtype == torch.uint8 and out.dtype == torch.uint8
         assert syms.is_contiguous() and out.is_contiguous()
@@ -455,9 +482,15 @@ class Encoder:
         tb = _TreeBuf()
         items = np.zeros((_nblocks(n, block_syms), 4), np.uint64)
         total = C.c_uint64(0)
-        rc = lib().hh_compress_blocks_device(self._h, syms.data_ptr() if n else None, n, block_syms, out.data_ptr(),
-                                             out.numel(), C.byref(tb), items.ctypes.data, C.byref(total),
-                                             s.cuda_stream)
+        if items_out is not None:
+            rc = lib().hh_compress_blocks_device_items(self._h, syms.data_ptr() if n else None, n, block_syms,
+                                                       out.data_ptr(), out.numel(), C.byref(tb),
+                                                       self._items_out_ptr(items_out, items.shape[0]),
+                                                       items.ctypes.data, C.byref(total), s.cuda_stream)
+        else:
+            rc = lib().hh_compress_blocks_device(self._h, syms.data_ptr() if n else None, n, block_syms,
+                                                 out.data_ptr(), out.numel(), C.byref(tb), items.ctypes.data,
+                                                 C.byref(total), s.cuda_stream)
         if rc == -5:
             e = HipHuffError(rc, "compress_blocks")
             e.tree, e.items, e.total_bytes = Tree._from_buf(tb), items, int(total.value)
@@ -545,12 +578,14 @@ class Decoder:
         self._tree = None
         self._pending = []          # buffers of asynchronous decodes, kept alive until wait()
         self._pinned = None         # (payload, out) FLAG_KEEP_HOST_PINNED keeps registered
+        self._batch_keep = None     # the tensors of the last decode_batch_items, which is not waited for
 
     def close(self):
         if self._h:
-            lib().hh_decoder_destroy(self._h)   # (waits for an asynchronous decode still running)
+            lib().hh_decoder_destroy(self._h)   # (waits for an asynchronous decode or items batch still running)
             self._h = C.c_void_p()
         self._pending = []
+        self._batch_keep = None
         self._pinned = None
 
     def __del__(self):
@@ -666,6 +701,62 @@ class Decoder:
             e.out_len, e.statuses = out_len, status
             raise e
         return out_len, status
+
+    def decode_batch_items(self, data, items, out, out_len=None, status=None, summary=False, stream=None,
+                           data_bytes: Optional[int] = None, out_bytes: Optional[int] = None) -> tuple:
+        """hh_decode_batch_device_items: decode_batch with the items, the
+        lengths and the statuses on the device, enqueued on stream (default:
+        the current one) without synchronising.  items: a CUDA int64 (n, 4)
+        tensor of (data_off, bits, out_off, cap) rows (values below 2^63);
+        out_len (int64, n) and status (int32, n): CUDA tensors, allocated
+        when not given (in the stream's pool).  Returns (out_len, status),
+        with summary=True or summary=<an int32[6] CUDA tensor> (out_len,
+        status, summary): the tensor holds hh_batch_summary
+        (batch_summary() reads it).  All of them are
+        complete once the stream has passed the call's work.  An item that
+        breaks a rule gets status -1 and length 0 and the others decode;
+        only what the host can check raises.  data_bytes / out_bytes: the
+        sizes the items are checked against (default: the tensors').  The
+        tensors are kept alive until the next batch call on this decoder or
+        close()."""
+        import torch
+        assert data.is_cuda and out.is_cuda and data.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert data.is_contiguous() and out.is_contiguous()
+        if not (items.is_cuda and items.dtype == torch.int64 and items.is_contiguous() and items.dim() == 2
+                and items.shape[1] == 4):
+            raise ValueError("items: a contiguous CUDA int64 tensor of (data_off, bits, out_off, cap) rows")
+        n = items.shape[0]
+        s = stream if stream is not None else torch.cuda.current_stream(data.device)
+        with torch.cuda.stream(s):
+            if out_len is None:
+                out_len = torch.empty(n, dtype=torch.int64, device=data.device)
+            if status is None:
+                status = torch.empty(n, dtype=torch.int32, device=data.device)
+            if summary is True:
+                summ = torch.empty(6, dtype=torch.int32, device=data.device)
+            else:
+                summ = None if summary is False or summary is None else summary
+        assert summ is None or (summ.is_cuda and summ.dtype == torch.int32 and summ.is_contiguous()
+                                and summ.numel() == 6)
+        assert out_len.is_cuda and out_len.dtype == torch.int64 and out_len.is_contiguous() and out_len.numel() == n
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == n
+        self._batch_keep = (data, items, out, out_len, status, summ)
+        rc = lib().hh_decode_batch_device_items(
+            self._h, data.data_ptr(), data.numel() if data_bytes is None else data_bytes,
+            items.data_ptr() if n else None, n, out.data_ptr(), out.numel() if out_bytes is None else out_bytes,
+            out_len.data_ptr() if n else None, status.data_ptr() if n else None,
+            summ.data_ptr() if summ is not None else None, s.cuda_stream)
+        _check(rc, "decode_batch_items")
+        return (out_len, status, summ) if summ is not None else (out_len, status)
+
+    @staticmethod
+    def batch_summary(summary) -> dict:
+        """The hh_batch_summary in decode_batch_items' summary tensor
+        (a copy to the host on the current stream: synchronise the batch's
+        stream first when it is another one)."""
+        w = summary.cpu().numpy().view(np.uint32)
+        return {"total_len": int(w[0]) | int(w[1]) << 32, "n_failed": int(w[2]), "first_failed": int(w[3]),
+                "first_status": int(w[4:5].view(np.int32)[0])}
 
     def batch_round_tiles(self) -> int:
         """hh_decode_batch_round_tiles: tiles per round of a workgroup of the

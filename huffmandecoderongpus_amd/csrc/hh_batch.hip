@@ -2,8 +2,9 @@
 // single launch (hh_decode_batch_device).  HIP (gfx950).
 //
 // k_batch: a workgroup of W waves takes streams from the descriptor list
-// (sorted by the host in descending length; workgroup b takes entries b,
-// b + grid, ...: nothing waits on another workgroup) and decodes each in
+// (longest first: sorted by the host, or bin-ordered on the device by
+// hh_batch_plan.hip for hh_decode_batch_device_items; workgroup b takes
+// entries b, b + grid, ...: nothing waits on another workgroup) and decodes each in
 // rounds of W tiles -- 64 W regions of S bits, lane = region -- by the rules
 // of hh_batch_algo.h: guess, count, fix rounds, scan, emission, copy-out.
 // The state entering the next round and the output base are carried from
@@ -34,20 +35,11 @@
 #include "hh_fsm_kern.h"
 
 #define HB_LDS (160u * 1024u)
-#define HB_UNTOUCHED 0x7fffffff     // a result slot the kernel did not write
 
 struct BatchGeo {
     uint32_t ns, K, r, S, G, W;
     uint32_t pay_off, misc_off, stg_off, stg_bytes;   // LDS byte offsets / the staging's size
     uint32_t n;
-};
-// a stream, in the kernel's order; idx: its index in the caller's list
-struct BatchDesc {
-    uint64_t data_off, bits, out_off, cap, idx;
-};
-struct BatchRes {
-    uint64_t len;
-    int64_t status;
 };
 
 // The emission sink: a step's symbols shifted into the current dword, which
@@ -215,29 +207,72 @@ void batch_setup(BatchDev *b, const FsmDev *fd, uint32_t G, uint32_t minlen) {
     b->ok = 1;
 }
 
+int batch_wait(BatchDev *b) {
+    if (!b->pend) return HH_OK;
+    b->pend = 0;
+    FS_OK(hipEventSynchronize(b->end));
+    return HH_OK;
+}
+
 void batch_free(BatchDev *b) {
     if (b->d_ws) (void)hipFree(b->d_ws);
     if (b->h_ws) (void)hipHostFree(b->h_ws);
+    if (b->end) (void)hipEventDestroy(b->end);
     memset(b, 0, sizeof(*b));
 }
 
-static int batch_ws(BatchDev *b, size_t need) {
-    if (b->d_size >= need) return HH_OK;
-    // (the call is synchronous and a pending asynchronous decode was checked
-    // before it: nothing on the device still uses the old workspace)
-    if (b->d_ws) FS_OK(hipFree(b->d_ws));
-    if (b->h_ws) FS_OK(hipHostFree(b->h_ws));
-    b->d_ws = b->h_ws = nullptr;
-    b->d_size = b->h_size = 0;
-    const size_t sz = need + need / 8;
-    if (hipMalloc(&b->d_ws, sz) != hipSuccess) return HH_ERR_NOMEM;
-    b->d_size = sz;
-    if (hipHostMalloc(&b->h_ws, sz, hipHostMallocDefault) != hipSuccess) {
-        b->h_ws = nullptr;
-        return HH_ERR_NOMEM;
+// The workspace: need_d device bytes, need_h pinned host bytes (the device
+// items' batch keeps nothing on the host).
+static int batch_ws(BatchDev *b, size_t need_d, size_t need_h) {
+    if (b->d_size < need_d) {
+        // (a synchronous call has returned, and a pending asynchronous decode
+        // does not use this workspace; a batch of device items may still run)
+        const int wrc = batch_wait(b);
+        if (wrc != HH_OK) return wrc;
+        if (b->d_ws) FS_OK(hipFree(b->d_ws));
+        b->d_ws = nullptr;
+        b->d_size = 0;
+        const size_t sz = need_d + need_d / 8;
+        if (hipMalloc(&b->d_ws, sz) != hipSuccess) return HH_ERR_NOMEM;
+        b->d_size = sz;
     }
-    b->h_size = sz;
+    if (b->h_size < need_h) {
+        if (b->h_ws) FS_OK(hipHostFree(b->h_ws));
+        b->h_ws = nullptr;
+        b->h_size = 0;
+        const size_t sz = need_h + need_h / 8;
+        if (hipHostMalloc(&b->h_ws, sz, hipHostMallocDefault) != hipSuccess) {
+            b->h_ws = nullptr;
+            return HH_ERR_NOMEM;
+        }
+        b->h_size = sz;
+    }
     return HH_OK;
+}
+
+// The resident workgroups of k_batch for the current tree, asked once.
+static int batch_grid(BatchDev *b) {
+    if (b->grid_max) return HH_OK;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, (const void *)k_batch) != hipSuccess || fa.sharedSizeBytes != 0) return HH_ERR_INTERNAL;
+    int per = 0, ncu = 0, dev = 0;
+    FS_OK(hipGetDevice(&dev));
+    FS_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_batch, (int)(64 * b->W), b->lds));
+    FS_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    if (per < 1 || ncu < 1) return HH_ERR_UNSUPPORTED;
+    b->grid_max = (uint32_t)(per * ncu);
+    return HH_OK;
+}
+
+static BatchGeo batch_geo(const BatchDev *b, const FsmDev *fd, uint64_t n) {
+    BatchGeo geo;
+    geo.ns = fd->ns; geo.K = fd->K; geo.r = fd->r; geo.S = fd->S; geo.G = b->G; geo.W = b->W;
+    geo.pay_off = emf_tab_bytes(fd->ns, fd->K, fd->r);
+    geo.misc_off = geo.pay_off + hb_pay_bytes(fd->S, b->W);
+    geo.stg_off = (geo.misc_off + hb_misc_bytes() + 15u) & ~15u;
+    geo.stg_bytes = hb_stage_bytes(fd->S, b->minlen, b->W);
+    geo.n = (uint32_t)n;
+    return geo;
 }
 
 int batch_decode(BatchDev *b, const FsmDev *fd, hipEvent_t *ev, const void *d_data, const hh_batch_item *items,
@@ -245,18 +280,10 @@ int batch_decode(BatchDev *b, const FsmDev *fd, hipEvent_t *ev, const void *d_da
                  uint64_t *lanes) {
     if (!b->ok) return HH_ERR_UNSUPPORTED;
     if (n > 0xffffffffull) return HH_ERR_UNSUPPORTED;
-    if (!b->grid_max) {
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, (const void *)k_batch) != hipSuccess || fa.sharedSizeBytes != 0) return HH_ERR_INTERNAL;
-        int per = 0, ncu = 0, dev = 0;
-        FS_OK(hipGetDevice(&dev));
-        FS_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_batch, (int)(64 * b->W), b->lds));
-        FS_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        if (per < 1 || ncu < 1) return HH_ERR_UNSUPPORTED;
-        b->grid_max = (uint32_t)(per * ncu);
-    }
+    const int grc = batch_grid(b);
+    if (grc != HH_OK) return grc;
     const size_t dbytes = (size_t)n * sizeof(BatchDesc), rbytes = (size_t)n * sizeof(BatchRes);
-    const int wrc = batch_ws(b, dbytes + rbytes);
+    const int wrc = batch_ws(b, dbytes + rbytes, dbytes + rbytes);
     if (wrc != HH_OK) return wrc;
     BatchDesc *hd = (BatchDesc *)b->h_ws;
     BatchRes *hr = (BatchRes *)((uint8_t *)b->h_ws + dbytes);
@@ -275,14 +302,10 @@ int batch_decode(BatchDev *b, const FsmDev *fd, hipEvent_t *ev, const void *d_da
         hr[k].status = HB_UNTOUCHED;
     }
     *lanes = regions;
-    BatchGeo geo;
-    geo.ns = fd->ns; geo.K = fd->K; geo.r = fd->r; geo.S = fd->S; geo.G = b->G; geo.W = b->W;
-    geo.pay_off = emf_tab_bytes(fd->ns, fd->K, fd->r);
-    geo.misc_off = geo.pay_off + hb_pay_bytes(fd->S, b->W);
-    geo.stg_off = (geo.misc_off + hb_misc_bytes() + 15u) & ~15u;
-    geo.stg_bytes = hb_stage_bytes(fd->S, b->minlen, b->W);
-    geo.n = (uint32_t)n;
+    const BatchGeo geo = batch_geo(b, fd, n);
     const FsmTab tab = {fd->ct, fd->b1, fd->tsym, fd->et, fd->er};
+    // a batch of device items still running reads the workspace this one overwrites
+    if (b->pend) FS_OK(hipStreamWaitEvent(st, b->end, 0));
     // descriptors and the untouched marks of the results, on the call's stream
     FS_OK(hipMemcpyAsync(dd, hd, dbytes + rbytes, hipMemcpyHostToDevice, st));
     const uint32_t grid = n < b->grid_max ? (uint32_t)n : b->grid_max;
@@ -293,6 +316,7 @@ int batch_decode(BatchDev *b, const FsmDev *fd, hipEvent_t *ev, const void *d_da
     FS_OK(hipEventRecord(ev[1], st));
     FS_OK(hipMemcpyAsync(hr, dr, rbytes, hipMemcpyDeviceToHost, st));
     FS_OK(hipStreamSynchronize(st));
+    b->pend = 0;                                          // (st waited for it, and is done)
     *ms = 0;
     (void)hipEventElapsedTime(ms, ev[0], ev[1]);
     int rc = HH_OK;
@@ -302,5 +326,47 @@ int batch_decode(BatchDev *b, const FsmDev *fd, hipEvent_t *ev, const void *d_da
         if (status) status[i] = s;
         if (s != HH_OK && rc == HH_OK) rc = s;
     }
+    return rc;
+}
+
+// Workspace of a batch of n device items: descriptors, results, the
+// descriptors in index order (the plan's first kernel is the only one that
+// reads the caller's list), a key byte per item, the plan's counters.
+int batch_decode_items(BatchDev *b, const FsmDev *fd, const void *d_data, uint64_t data_bytes,
+                       const hh_batch_item *d_items, uint64_t n, void *d_out, uint64_t out_bytes,
+                       uint64_t *d_out_len, int32_t *d_status, hh_batch_summary *d_summary, hipStream_t st) {
+    if (!b->ok) return HH_ERR_UNSUPPORTED;
+    if (n >= 0xffffffffull) return HH_ERR_UNSUPPORTED;    // (0xffffffff is the summary's "no stream")
+    const int grc = batch_grid(b);
+    if (grc != HH_OK) return grc;
+    if (!b->end) FS_OK(hipEventCreateWithFlags(&b->end, hipEventDisableTiming));
+    const size_t dbytes = (size_t)n * sizeof(BatchDesc), rbytes = (size_t)n * sizeof(BatchRes);
+    const size_t kbytes = ((size_t)n + 255u) & ~(size_t)255u;
+    const int wrc = batch_ws(b, 2 * dbytes + rbytes + kbytes + HB_PLAN_CTL_BYTES, 0);
+    if (wrc != HH_OK) return wrc;
+    uint8_t *w = (uint8_t *)b->d_ws;
+    BatchDesc *dd = (BatchDesc *)w;
+    BatchRes *dr = (BatchRes *)(w + dbytes);
+    BatchDesc *tmp = (BatchDesc *)(w + dbytes + rbytes);
+    uint8_t *key = w + 2 * dbytes + rbytes;
+    uint32_t *ctl = (uint32_t *)(key + kbytes);
+    // the batch before this one on another stream still uses the workspace
+    // (on the same stream the order is the stream's)
+    if (b->pend && b->pend_st != st) FS_OK(hipStreamWaitEvent(st, b->end, 0));
+    const uint64_t RB = (uint64_t)HB_NR * b->W * fd->S;
+    int rc = batch_plan_enqueue(d_items, (uint32_t)n, data_bytes, out_bytes, RB, dd, dr, tmp, key, ctl, d_summary, st);
+    if (rc == HH_OK) {
+        const BatchGeo geo = batch_geo(b, fd, n);
+        const FsmTab tab = {fd->ct, fd->b1, fd->tsym, fd->et, fd->er};
+        const uint32_t grid = n < b->grid_max ? (uint32_t)n : b->grid_max;
+        hipLaunchKernelGGL(k_batch, dim3(grid), dim3(64 * b->W), b->lds, st, (const uint8_t *)d_data, dd, dr,
+                           (uint8_t *)d_out, tab, geo);
+        if (hipGetLastError() != hipSuccess) rc = HH_ERR_DEVICE;
+    }
+    if (rc == HH_OK) rc = batch_results_enqueue(dr, key, (uint32_t)n, d_out_len, d_status, d_summary, ctl, st);
+    // (also after a failed launch: what was enqueued before it uses the workspace)
+    FS_OK(hipEventRecord(b->end, st));
+    b->pend = 1;
+    b->pend_st = st;
     return rc;
 }

@@ -70,6 +70,7 @@ extern "C" void hh_decoder_destroy(hh_decoder *d) {
     if (!d) return;
     hipSetDevice(d->device);
     async_check(d);                     // (an asynchronous decode still running)
+    (void)batch_wait(&d->batch);        // (a batch of device items still running)
     hh_decoder_release_host(d);
     if (d->ws) hipFree(d->ws);
     if (d->d_l1) hipFree(d->d_l1);
@@ -131,7 +132,9 @@ extern "C" int hh_decoder_set_tree(hh_decoder *d, const hh_tree *tree) {
     if (!d || !tree) return HH_ERR_ARG;
     HIP_OK(hipSetDevice(d->device));
     async_check(d);                     // (a pending asynchronous decode uses the current tables)
-    int rc = hh_tables_build(tree, d->ht);
+    int rc = batch_wait(&d->batch);     // (and so does a batch of device items)
+    if (rc) return rc;
+    rc = hh_tables_build(tree, d->ht);
     if (rc) return rc;
     HIP_OK(hipSetDevice(d->device));
     HIP_OK(hipMemcpy(d->d_l1, d->ht->l1, sizeof(uint64_t) * HH_L1_SIZE, hipMemcpyHostToDevice));
@@ -498,6 +501,32 @@ extern "C" int hh_decode_batch_device(hh_decoder *d, const void *d_data, uint64_
     for (uint64_t i = 0; i < n; i++) d->stats.out_len += out_len[i];
     d->stats.state_machine = 3;
     return rc;
+}
+
+// The batch from a device list: only what the host can know is checked here;
+// the items are checked by the kernel that reads them (hh_batch_plan.hip).
+// Nothing here waits for the device, and a pending asynchronous decode stays
+// pending (it shares no workspace with the batch).
+extern "C" int hh_decode_batch_device_items(hh_decoder *d, const void *d_data, uint64_t data_bytes,
+                                            const hh_batch_item *d_items, uint64_t n, void *d_out,
+                                            uint64_t out_bytes, uint64_t *d_out_len, int32_t *d_status,
+                                            hh_batch_summary *d_summary, void *hip_stream) {
+    if (!d) return HH_ERR_ARG;
+    if (n == 0) {
+        if (!d_summary) return HH_OK;
+        HIP_OK(hipSetDevice(d->device));
+        return batch_summary_clear(d_summary, (hipStream_t)hip_stream);
+    }
+    if (!d_items || !d_out_len || !d_status || !d_data || !d_out || !d->have_tree) return HH_ERR_ARG;
+    if (((uintptr_t)d_data & 3u) != 0) return HH_ERR_ARG;   // word loads
+    if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;
+    HIP_OK(hipSetDevice(d->device));
+    const int rc = batch_decode_items(&d->batch, &d->fsm, d_data, data_bytes, d_items, n, d_out, out_bytes, d_out_len,
+                                      d_status, d_summary, (hipStream_t)hip_stream);
+    if (rc != HH_OK) return rc;
+    memset(&d->stats, 0, sizeof(d->stats));                // (the host knows no lengths)
+    d->stats.state_machine = 3;
+    return HH_OK;
 }
 
 extern "C" int hh_decode_batch_round_tiles(const hh_decoder *d, uint32_t *tiles) {

@@ -20,7 +20,9 @@
 //                atomic ORs on its first and last word (pieces of one block
 //                share words, blocks never do; the output is zeroed first).
 // The blocks' bits, the totals and the flag come back in copies on the same
-// stream; the host fills the hh_batch_item list.
+// stream; the host fills the hh_batch_item list.  The _items entries also
+// leave that list on the device (k_encb_items, after the scan), where
+// hh_decode_batch_device_items takes it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -191,11 +193,25 @@ __global__ __launch_bounds__(ENC_TB) void k_encb_pack(const uint8_t *__restrict_
     }
 }
 
-extern "C" int hh_encoder_encode_blocks(hh_encoder *enc, const hh_tree *tree, const void *d_syms, uint64_t n,
-                                        uint64_t block_syms, void *d_out, uint64_t cap, hh_batch_item *items,
-                                        uint64_t *total_bytes, void *hip_stream) {
-    if (!enc || !tree || !total_bytes || block_syms == 0 || (n && (!d_syms || !items)) || (!d_out && cap))
-        return HH_ERR_ARG;
+// The items on the device, from the scan's arrays: what the host writes into
+// its list from the blocks' bits (encode_blocks below), a thread per block.
+__global__ __launch_bounds__(ENC_SCAN_TB) void k_encb_items(const uint64_t *__restrict__ bbits,
+                                                            const uint64_t *__restrict__ wb, uint64_t nb, uint64_t n,
+                                                            uint64_t block_syms, hh_batch_item *__restrict__ items) {
+    const uint64_t b = (uint64_t)blockIdx.x * ENC_SCAN_TB + threadIdx.x;
+    if (b >= nb) return;
+    items[b] = hh_batch_item{4u * wb[b], bbits[b], b * block_syms, b + 1 < nb ? block_syms : n - b * block_syms};
+}
+
+// hh_encoder_encode_blocks (items on the host) and hh_encoder_encode_blocks_items
+// (d_items on the device too; items may then be NULL).  The blocks' bits stay
+// in enc->host_bits.
+static int encode_blocks(hh_encoder *enc, const hh_tree *tree, const void *d_syms, uint64_t n, uint64_t block_syms,
+                         void *d_out, uint64_t cap, hh_batch_item *d_items, bool to_device, hh_batch_item *items,
+                         uint64_t *total_bytes, void *hip_stream) {
+    if (!enc || !tree || !total_bytes || block_syms == 0 || (!d_out && cap)) return HH_ERR_ARG;
+    if (n && (!d_syms || (to_device ? !d_items : !items))) return HH_ERR_ARG;
+    if (((uintptr_t)d_items & 7u) != 0) return HH_ERR_ARG;  // (64-bit stores)
     if (((uintptr_t)d_out & 3u) != 0) return HH_ERR_ARG;   // (32-bit word stores)
     *total_bytes = 0;
     EncTab h;
@@ -247,6 +263,11 @@ extern "C" int hh_encoder_encode_blocks(hh_encoder *enc, const hh_tree *tree, co
         hipLaunchKernelGGL(k_encb_scan, dim3(1), dim3(ENC_SCAN_TB), 0, st, d_S, npc, (uint32_t)ppb, nb, d_bb, d_wb,
                            d_res);
         if (hipGetLastError() != hipSuccess) break;
+        if (to_device) {
+            hipLaunchKernelGGL(k_encb_items, dim3((unsigned)((nb + ENC_SCAN_TB - 1) / ENC_SCAN_TB)), dim3(ENC_SCAN_TB),
+                               0, st, d_bb, d_wb, nb, n, block_syms, d_items);
+            if (hipGetLastError() != hipSuccess) break;
+        }
         if (hipMemcpyAsync(enc->host_bits, d_bb, nb * 8, hipMemcpyDeviceToHost, st) != hipSuccess) break;
         if (hipMemcpyAsync(hres, d_res, 40, hipMemcpyDeviceToHost, st) != hipSuccess) break;
         if (hipStreamSynchronize(st) != hipSuccess) break;
@@ -254,10 +275,12 @@ extern "C" int hh_encoder_encode_blocks(hh_encoder *enc, const hh_tree *tree, co
         uint64_t off = 0, sum = 0;
         for (uint64_t b = 0; b < nb; b++) {
             const uint64_t bits = enc->host_bits[b];
-            items[b].data_off = off;
-            items[b].bits = bits;
-            items[b].out_off = b * block_syms;
-            items[b].cap = b + 1 < nb ? block_syms : n - b * block_syms;
+            if (items) {
+                items[b].data_off = off;
+                items[b].bits = bits;
+                items[b].out_off = b * block_syms;
+                items[b].cap = b + 1 < nb ? block_syms : n - b * block_syms;
+            }
             off += (bits + 31) / 32 * 4;
             sum += bits;
         }
@@ -272,6 +295,18 @@ extern "C" int hh_encoder_encode_blocks(hh_encoder *enc, const hh_tree *tree, co
         rc = HH_OK;
     } while (0);
     return rc;
+}
+
+extern "C" int hh_encoder_encode_blocks(hh_encoder *enc, const hh_tree *tree, const void *d_syms, uint64_t n,
+                                        uint64_t block_syms, void *d_out, uint64_t cap, hh_batch_item *items,
+                                        uint64_t *total_bytes, void *hip_stream) {
+    return encode_blocks(enc, tree, d_syms, n, block_syms, d_out, cap, nullptr, false, items, total_bytes, hip_stream);
+}
+
+extern "C" int hh_encoder_encode_blocks_items(hh_encoder *enc, const hh_tree *tree, const void *d_syms, uint64_t n,
+                                              uint64_t block_syms, void *d_out, uint64_t cap, hh_batch_item *d_items,
+                                              hh_batch_item *items, uint64_t *total_bytes, void *hip_stream) {
+    return encode_blocks(enc, tree, d_syms, n, block_syms, d_out, cap, d_items, true, items, total_bytes, hip_stream);
 }
 
 // Compress into blocks: one histogram of all n bytes and one tree for all the
@@ -289,10 +324,11 @@ extern "C" uint64_t hh_compress_blocks_bound(uint64_t n, uint64_t block_syms) {
     return (n + 3) / 4 * 4 + 4 * (n / block_syms + (n % block_syms != 0));
 }
 
-extern "C" int hh_compress_blocks_device(hh_encoder *enc, const void *d_syms, uint64_t n, uint64_t block_syms,
-                                         void *d_out, uint64_t cap, hh_tree_buf *tree, hh_batch_item *items,
-                                         uint64_t *total_bytes, void *hip_stream) {
-    if (!enc || !d_syms || !tree || !items || !total_bytes || n == 0 || block_syms == 0 || (!d_out && cap))
+static int compress_blocks(hh_encoder *enc, const void *d_syms, uint64_t n, uint64_t block_syms, void *d_out,
+                           uint64_t cap, hh_tree_buf *tree, hh_batch_item *d_items, bool to_device,
+                           hh_batch_item *items, uint64_t *total_bytes, void *hip_stream) {
+    if (!enc || !d_syms || !tree || (to_device ? !d_items : !items) || !total_bytes || n == 0 || block_syms == 0 ||
+        (!d_out && cap))
         return HH_ERR_ARG;
     if (((uintptr_t)d_out & 3u) != 0) return HH_ERR_ARG;   // (32-bit word stores)
     *total_bytes = 0;
@@ -308,11 +344,25 @@ extern "C" int hh_compress_blocks_device(hh_encoder *enc, const void *d_syms, ui
     if (rc) return rc;
     uint64_t pred = 0;
     for (int s = 0; s < 256; s++) pred += counts[s] * len8[s];   // (<= 64 n < 2^43)
-    rc = hh_encoder_encode_blocks(enc, &t, d_syms, n, block_syms, d_out, cap, items, total_bytes, hip_stream);
+    rc = encode_blocks(enc, &t, d_syms, n, block_syms, d_out, cap, d_items, to_device, items, total_bytes, hip_stream);
     if (rc != HH_OK && rc != HH_ERR_CAPACITY) return rc;
     const uint64_t nb = n / block_syms + (n % block_syms != 0);
     uint64_t got = 0;
-    for (uint64_t b = 0; b < nb; b++) got += items[b].bits;
+    for (uint64_t b = 0; b < nb; b++) got += enc->host_bits[b];   // (the items' bits)
     if (got != pred) return HH_ERR_INTERNAL;
     return rc;
+}
+
+extern "C" int hh_compress_blocks_device(hh_encoder *enc, const void *d_syms, uint64_t n, uint64_t block_syms,
+                                         void *d_out, uint64_t cap, hh_tree_buf *tree, hh_batch_item *items,
+                                         uint64_t *total_bytes, void *hip_stream) {
+    return compress_blocks(enc, d_syms, n, block_syms, d_out, cap, tree, nullptr, false, items, total_bytes,
+                           hip_stream);
+}
+
+extern "C" int hh_compress_blocks_device_items(hh_encoder *enc, const void *d_syms, uint64_t n, uint64_t block_syms,
+                                               void *d_out, uint64_t cap, hh_tree_buf *tree, hh_batch_item *d_items,
+                                               hh_batch_item *items, uint64_t *total_bytes, void *hip_stream) {
+    return compress_blocks(enc, d_syms, n, block_syms, d_out, cap, tree, d_items, true, items, total_bytes,
+                           hip_stream);
 }

@@ -361,6 +361,67 @@ int hh_decode_batch_device(hh_decoder *dec, const void *d_data, uint64_t data_by
  * length changes its number of rounds.  HH_ERR_UNSUPPORTED as above. */
 int hh_decode_batch_round_tiles(const hh_decoder *dec, uint32_t *tiles);
 
+/* What a batch of device items came to, for a caller that reads one record
+ * instead of two arrays (hh_decode_batch_device_items writes it on the
+ * device, in stream order, like the arrays). */
+typedef struct {
+    uint64_t total_len;      /* sum of out_len over the streams with status HH_OK or HH_ERR_CAPACITY */
+    uint32_t n_failed;       /* streams whose status != HH_OK */
+    uint32_t first_failed;   /* lowest such index (0xffffffff: none) */
+    int32_t  first_status;   /* its status (HH_OK: none) */
+    uint32_t pad;
+} hh_batch_summary;
+
+/* hh_decode_batch_device with everything per stream on the device and in
+ * stream order: d_items, d_out_len and d_status are device arrays of n,
+ * d_summary a device record (may be NULL; 8-byte aligned).  Stream i gives
+ * the bytes, d_out_len[i] and d_status[i] that hh_decode_batch_device gives
+ * for the same item -- per-stream capacity, bits == 0, outputs that touch at
+ * any alignment, the same trees (HH_ERR_UNSUPPORTED otherwise), n < 2^32 - 1.
+ * Stream ordered: everything is enqueued on hip_stream and the call returns
+ * without waiting for the device.  d_items and d_data are read in the order
+ * of hip_stream (work queued before the call on that stream may still be
+ * producing them); d_out, d_out_len, d_status and d_summary are complete when
+ * the stream reaches the end of the call's work.  The call issues no stream,
+ * device or event synchronisation and no device-to-host copy, and puts
+ * nothing on the null stream -- with one exception: a call that must grow
+ * the decoder's batch workspace waits for the previous batch's end before it
+ * frees the old one; a call that finds the workspace large enough never
+ * blocks.  d_items must stay valid until the stream has passed the call's
+ * first kernel (the only one that reads it); d_data and the result arrays
+ * until the end of the call's work.
+ * Checked on the host, before anything is enqueued: HH_ERR_ARG for a null
+ * pointer with n > 0 (d_summary excepted), d_data off a 4-byte boundary, no
+ * tree set; HH_ERR_UNSUPPORTED for a tree the batch cannot take or n >= 2^32
+ * - 1.  n == 0 returns HH_OK and enqueues nothing, except that a d_summary
+ * given is set to the empty summary {0, 0, 0xffffffff, HH_OK} (memsets on
+ * hip_stream).
+ * Checked on the device, per item (the host never sees the items): the
+ * three rules of hh_decode_batch_device -- data_off a multiple of 4; for
+ * bits > 0, data_off + ceil(bits/8) + HH_PAYLOAD_PAD <= data_bytes; out_off
+ * + cap <= out_bytes, none of the sums overflowing.  An item that breaks one
+ * gets d_status[i] = HH_ERR_ARG and d_out_len[i] = 0; not a byte is read or
+ * written for it, and the other streams decode normally.  (The one
+ * deliberate difference from hh_decode_batch_device, which rejects the whole
+ * batch.)  A slot the decode kernel did not reach reports HH_ERR_INTERNAL.
+ * The return value says what was enqueued, never how the streams fared:
+ * that is in d_status and d_summary.
+ * With the decoder's other calls: the decoder records an event after the
+ * batch's last kernel.  hh_decoder_set_tree and hh_decoder_destroy wait for
+ * it on the host; hh_decode_batch_device and an hh_decode_batch_device_items
+ * on another stream make their stream wait for it (the batch workspace is
+ * one per decoder); a later items batch on the same stream is ordered by the
+ * stream.  The single-stream decodes do not share that workspace and need no
+ * wait; a pending hh_decode_device_async is not checked by this call and
+ * stays pending.  hh_stats after the call: all zero but state_machine = 3
+ * (the host knows no lengths). */
+int hh_decode_batch_device_items(hh_decoder *dec, const void *d_data, uint64_t data_bytes,
+                                 const hh_batch_item *d_items /* device, n */, uint64_t n,
+                                 void *d_out, uint64_t out_bytes,
+                                 uint64_t *d_out_len /* device, n */, int32_t *d_status /* device, n */,
+                                 hh_batch_summary *d_summary /* device, may be NULL */,
+                                 void *hip_stream);
+
 /* ---------------------------------------------------------------------- */
 /* Blocked encode: the producer of a batch.  n symbols are cut into       */
 /* nb = ceil(n / block_syms) blocks, block b the symbols                  */
@@ -401,6 +462,18 @@ int hh_encoder_encode_blocks(hh_encoder *enc, const hh_tree *tree, const void *d
                              uint64_t block_syms, void *d_out, uint64_t cap,
                              hh_batch_item *items /* host, nb */, uint64_t *total_bytes,
                              void *hip_stream);
+/* hh_encoder_encode_blocks that also leaves the items on the device: d_items
+ * (device, nb entries, 8-byte aligned; required when n > 0) receives the same
+ * items[b], written by a kernel from the block scan's arrays, and goes
+ * straight into hh_decode_batch_device_items with no upload.  items (host)
+ * may be NULL.  Everything else -- synchronous, the capacity rule, the
+ * errors, what HH_ERR_CAPACITY leaves filled (d_items too) -- as
+ * hh_encoder_encode_blocks. */
+int hh_encoder_encode_blocks_items(hh_encoder *enc, const hh_tree *tree, const void *d_syms, uint64_t n,
+                                   uint64_t block_syms, void *d_out, uint64_t cap,
+                                   hh_batch_item *d_items /* device, nb */,
+                                   hh_batch_item *items /* host, nb, may be NULL */,
+                                   uint64_t *total_bytes, void *hip_stream);
 /* Compress into blocks: the histogram of all n > 0 bytes, hh_tree_build, then
  * hh_encoder_encode_blocks with that one tree, which *tree receives (also
  * with HH_ERR_CAPACITY).  The blocks' bits must add up to the histogram's
@@ -418,6 +491,13 @@ int hh_compress_blocks_device(hh_encoder *enc, const void *d_syms, uint64_t n, u
                               void *d_out, uint64_t cap, hh_tree_buf *tree,
                               hh_batch_item *items /* host, nb */, uint64_t *total_bytes,
                               void *hip_stream);
+/* The same chain with hh_encoder_encode_blocks_items at its end: d_items
+ * (device, nb) is filled, items (host) may be NULL. */
+int hh_compress_blocks_device_items(hh_encoder *enc, const void *d_syms, uint64_t n, uint64_t block_syms,
+                                    void *d_out, uint64_t cap, hh_tree_buf *tree,
+                                    hh_batch_item *d_items /* device, nb */,
+                                    hh_batch_item *items /* host, nb, may be NULL */,
+                                    uint64_t *total_bytes, void *hip_stream);
 
 /* ---------------------------------------------------------------------- */
 /* Segments (multi-GPU shards).  The stream is cut into tiles of           */

@@ -144,6 +144,9 @@ _SIGS = {
                                 C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_void_p], C.c_int),
     "hh_decode_batch_device_items": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                       C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hh_decode_blocks_read": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                               C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                              C.c_int),
     "hh_decode_batch_round_tiles": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     "hh_decoder_tile_bits": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hh_decode_device_range": ([C.c_void_p, C.c_void_p, C.POINTER(_Range), C.c_void_p,
@@ -749,9 +752,68 @@ class Decoder:
         _check(rc, "decode_batch_items")
         return (out_len, status, summ) if summ is not None else (out_len, status)
 
+    def read_blocks(self, data, index, n_syms: int, block_syms: int, reads, out, read_len=None, status=None,
+                    summary=False, stream=None, data_bytes: Optional[int] = None,
+                    out_bytes: Optional[int] = None) -> tuple:
+        """hh_decode_blocks_read: byte ranges of the uncompressed data of a
+        block-coded buffer, each delivered to its own place in out, enqueued
+        on stream (default: the current one) without synchronising.  data:
+        the blocks' payload; index: the CUDA int64 (nb, 4) tensor that
+        Encoder.encode_blocks(..., items_out=t) fills, for n_syms symbols in
+        blocks of block_syms; reads: a CUDA int64 (m, 3) tensor of (src_off,
+        len, dst_off) rows (a host array of that shape is uploaded on the
+        call's stream).  read_len (int64, m), status (int32, m) and summary
+        as in decode_batch_items.  Returns (read_len, status[, summary]),
+        complete once the stream has passed the call's work.  A read that
+        breaks a rule gets status -1, one whose block ends early -3
+        (read_len the bytes delivered), and the others are served; only what
+        the host can check raises.  The tensors are kept alive until the
+        next batch call on this decoder or close()."""
+        import torch
+        assert data.is_cuda and out.is_cuda and data.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert data.is_contiguous() and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(data.device)
+        if not torch.is_tensor(reads):
+            h = np.ascontiguousarray(reads)
+            if h.ndim != 2 or h.shape[1] != 3:
+                raise ValueError("reads: an (m, 3) array of (src_off, len, dst_off)")
+            h = h.astype(np.uint64, copy=False).view(np.int64)
+            with torch.cuda.stream(s):
+                reads = torch.from_numpy(h).to(data.device, non_blocking=True)
+        if not (reads.is_cuda and reads.dtype == torch.int64 and reads.is_contiguous() and reads.dim() == 2
+                and reads.shape[1] == 3):
+            raise ValueError("reads: a contiguous CUDA int64 tensor of (src_off, len, dst_off) rows")
+        nb = _nblocks(n_syms, block_syms) if block_syms > 0 else index.shape[0]
+        if not (index.is_cuda and index.dtype == torch.int64 and index.is_contiguous()
+                and tuple(index.shape) == (nb, 4)):
+            raise ValueError(f"index: a contiguous CUDA int64 tensor of shape ({nb}, 4)")
+        m = reads.shape[0]
+        with torch.cuda.stream(s):
+            if read_len is None:
+                read_len = torch.empty(m, dtype=torch.int64, device=data.device)
+            if status is None:
+                status = torch.empty(m, dtype=torch.int32, device=data.device)
+            if summary is True:
+                summ = torch.empty(6, dtype=torch.int32, device=data.device)
+            else:
+                summ = None if summary is False or summary is None else summary
+        assert summ is None or (summ.is_cuda and summ.dtype == torch.int32 and summ.is_contiguous()
+                                and summ.numel() == 6)
+        assert read_len.is_cuda and read_len.dtype == torch.int64 and read_len.is_contiguous() and read_len.numel() == m
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == m
+        self._batch_keep = (data, index, reads, out, read_len, status, summ)
+        rc = lib().hh_decode_blocks_read(
+            self._h, data.data_ptr(), data.numel() if data_bytes is None else data_bytes,
+            index.data_ptr() if nb else None, n_syms, block_syms, reads.data_ptr() if m else None, m,
+            out.data_ptr(), out.numel() if out_bytes is None else out_bytes,
+            read_len.data_ptr() if m else None, status.data_ptr() if m else None,
+            summ.data_ptr() if summ is not None else None, s.cuda_stream)
+        _check(rc, "read_blocks")
+        return (read_len, status, summ) if summ is not None else (read_len, status)
+
     @staticmethod
     def batch_summary(summary) -> dict:
-        """The hh_batch_summary in decode_batch_items' summary tensor
+        """The hh_batch_summary in decode_batch_items' or read_blocks' summary tensor
         (a copy to the host on the current stream: synchronise the batch's
         stream first when it is another one)."""
         w = summary.cpu().numpy().view(np.uint32)

@@ -13,9 +13,13 @@
 
 #define HB_UNTOUCHED 0x7fffffff     // a result slot the kernel did not write
 
-// a stream, in the kernel's order; idx: its index in the caller's list
+// a stream, in the kernel's order; idx: its index in the caller's list.
+// win != 0: a window piece (hh_decode_blocks_read) -- of the stream's symbols
+// only [skip, skip + cap) are wanted, at out_off; the result's len is the
+// bytes delivered.  win == 0 (skip 0): a whole stream clipped to cap.
 struct BatchDesc {
-    uint64_t data_off, bits, out_off, cap, idx;
+    uint64_t data_off, bits, out_off, cap, idx, skip;
+    uint32_t win, pad;
 };
 struct BatchRes {
     uint64_t len;
@@ -60,16 +64,62 @@ int batch_decode_items(BatchDev *b, const FsmDev *fd, const void *d_data, uint64
                        const hh_batch_item *d_items, uint64_t n, void *d_out, uint64_t out_bytes,
                        uint64_t *d_out_len, int32_t *d_status, hh_batch_summary *d_summary, hipStream_t st);
 
+// Range reads over a blocked buffer (hh_decode_blocks_read), all of it
+// enqueued on st: the plan (reads -> window pieces, hh_batch_read.hip), the
+// bin order, k_batch over the P slots of the piece budget, the gather of the
+// pieces' results into d_read_len / d_status / d_summary (may be NULL).
+int batch_decode_read(BatchDev *b, const FsmDev *fd, const void *d_data, uint64_t data_bytes,
+                      const hh_batch_item *d_index, uint64_t n_syms, uint64_t block_syms, const hh_block_read *d_reads,
+                      uint64_t m, uint32_t P, void *d_out, uint64_t out_bytes, uint64_t *d_read_len,
+                      int32_t *d_status, hh_batch_summary *d_summary, hipStream_t st);
+
 // hh_batch_plan.hip: the kernels around k_batch of a batch of device items.
 // key: a byte per item (hh_batch_plan_algo.h), tmp: the descriptors in index
 // order, ctl: HB_PLAN_CTL_BYTES of counters.
 #define HB_PLAN_CTL_BYTES 1024u
+// ctl's u32 words: the streams per bin, the bins' placement cursors, the
+// results' workgroups finished; for range reads the slots that hold a piece
+// and (two words, 8-byte aligned) the first failing read << 32 | -status
+#define HB_CTL_CNT 0u
+#define HB_CTL_CUR 64u
+#define HB_CTL_DONE 128u
+#define HB_CTL_TOTAL 130u
+#define HB_CTL_FIRST 132u
 int batch_plan_enqueue(const hh_batch_item *d_items, uint32_t n, uint64_t data_bytes, uint64_t out_bytes,
                        uint64_t round_bits, BatchDesc *desc, BatchRes *res, BatchDesc *tmp, uint8_t *key,
                        uint32_t *ctl, hh_batch_summary *d_summary, hipStream_t st);
 int batch_results_enqueue(const BatchRes *res, const uint8_t *key, uint32_t n, uint64_t *d_out_len,
                           int32_t *d_status, hh_batch_summary *d_summary, uint32_t *ctl, hipStream_t st);
+// k_plan_place alone: tmp[0..n) by their key bytes into desc; ctl's counts
+// per bin are the caller's (batch_plan_enqueue's k_plan_count, or the range
+// reads' k_read_fill).
+int batch_place_enqueue(const BatchDesc *tmp, const uint8_t *key, uint32_t n, uint32_t *ctl, BatchDesc *desc,
+                        hipStream_t st);
 // The empty summary into d_summary, in the order of st.
 int batch_summary_clear(hh_batch_summary *d_summary, hipStream_t st);
+
+
+// hh_batch_read.hip: the plan of a range read and the gather of its results.
+// The workspace beside desc / res / tmp / key / ctl (which are the items
+// batch's, for P slots): per slot the owning read, per read its first slot,
+// its copy, its record and its own status.
+struct ReadWs {
+    BatchDesc *desc, *tmp;
+    BatchRes *res;
+    uint64_t *start;         // m: a read's piece count, then (k_read_scan) its first slot
+    hh_block_read *reads;    // m: the caller's list, copied by the one kernel that reads it
+    uint64_t *rec;           // 2 m: delivered bytes; min over failing pieces of (block ordinal << 8 | -status)
+    uint32_t *own;           // P: a slot's read
+    int32_t *rstat;          // m: HH_ERR_ARG for a read that gets no piece, else HH_OK
+    uint32_t *ctl;
+    uint8_t *key;
+};
+size_t read_ws_bytes(uint64_t m, uint32_t P);
+void read_ws_carve(ReadWs *w, void *d_ws, uint64_t m, uint32_t P);
+int read_plan_enqueue(const ReadWs *w, const hh_batch_item *d_index, uint64_t data_bytes, uint64_t n_syms,
+                      uint64_t block_syms, const hh_block_read *d_reads, uint32_t m, uint32_t P, uint64_t out_bytes,
+                      uint64_t round_bits, hh_batch_summary *d_summary, hipStream_t st);
+int read_results_enqueue(const ReadWs *w, uint32_t m, uint32_t P, uint64_t *d_read_len, int32_t *d_status,
+                         hh_batch_summary *d_summary, hipStream_t st);
 
 #endif

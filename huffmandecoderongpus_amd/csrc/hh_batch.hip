@@ -18,6 +18,14 @@
 //   wx[16] waves' exit states, wt[16] waves' counts, chg[3] fix-round flags
 //   the round's staging: its symbols at their output address mod 16
 //
+// Window pieces (hh_decode_blocks_read; hh_batch_read.hip makes them): a
+// descriptor with `win` set wants the stream's symbols [skip, skip + cap)
+// only.  Rounds before the window are counted and not emitted, of the others
+// the window's bytes alone are copied out (hb_window), and the piece ends
+// after the round that fills the window: later rounds are neither loaded nor
+// walked.  Its result is the bytes delivered, HH_ERR_FORMAT when the stream
+// ended before the window was full.
+//
 // Output edges: neighbouring streams' outputs may share a dword (any out_off,
 // exact capacities) and another workgroup writes the neighbour, so the
 // copy-out stores whole 16-byte blocks only where all 16 bytes are this
@@ -92,9 +100,12 @@ __global__ __launch_bounds__(64 * HB_WMAX) void k_batch(const uint8_t *__restric
     for (uint32_t it = blockIdx.x; it < geo.n; it += gridDim.x) {
         const uint64_t data_off = uni64(desc[it].data_off), bits = uni64(desc[it].bits);
         const uint64_t out_off = uni64(desc[it].out_off), cap = uni64(desc[it].cap), idx = uni64(desc[it].idx);
+        // a window piece wants the stream's symbols [skip, skip + cap) only (else skip is 0)
+        const uint64_t skip = uni64(desc[it].skip);
+        const bool win = __builtin_amdgcn_readfirstlane((int)desc[it].win) != 0;
         const uint32_t *g = (const uint32_t *)(data + data_off);
-        const uint64_t nwords = (bits + 31u) / 32u, rounds = (bits + RB - 1u) / RB;
-        uint64_t base = 0;                                // symbols before the round
+        const uint64_t nwords = (bits + 31u) / 32u, rounds = win && !cap ? 0u : (bits + RB - 1u) / RB;
+        uint64_t base = 0, got = 0;                       // symbols before the round; bytes delivered
         uint32_t carry = 0, fail = lds0 ? 0u : 1u;        // the state entering the round
         for (uint64_t rd = 0; rd < rounds; rd++) {
             const uint64_t R0 = rd * RB, R = R0 + (uint64_t)jr * S;
@@ -154,10 +165,15 @@ __global__ __launch_bounds__(64 * HB_WMAX) void k_batch(const uint8_t *__restric
                 tot += t;
             }
             const uint32_t L = woff + incl - n;
-            // emission into the staging, at the output's address mod 16
-            uint8_t *gp = out + out_off + base;
-            const uint32_t a0 = (uint32_t)((uintptr_t)gp & 15u);
-            const uint32_t keep = hb_clip(base, tot, cap);
+            // emission into the staging, at the output's address mod 16: the
+            // round's byte t at a0 + t.  ga is the address of t = 0, which for
+            // a round that starts before the window is no address of the
+            // buffer (unsigned arithmetic; only the window's bytes, from
+            // `from` on, are ever stored)
+            const uintptr_t ga = (uintptr_t)out + out_off + base - skip;
+            const uint32_t a0 = (uint32_t)(ga & 15u);
+            uint32_t from;
+            const uint32_t keep = hb_window(base, tot, skip, cap, &from);
             if (a0 + tot + 8u > geo.stg_bytes) fail = 1u;       // (the host sized it for the most a round holds)
             if (!fail && keep) {
                 if (tid == 0) *(uint32_t *)(stg + ((a0 + tot) & ~3u)) = 0u;   // the last, partial dword: ORs only
@@ -169,25 +185,28 @@ __global__ __launch_bounds__(64 * HB_WMAX) void k_batch(const uint8_t *__restric
                 __syncthreads();
                 if (sink.sh) atomicOr((uint32_t *)(smem + sink.wd), sink.a);
                 __syncthreads();
-                // copy-out: whole 16-B blocks inside [a0, end), bytes at the edges
-                uint8_t *gb = gp - a0;
-                const uint32_t end = a0 + keep, nq = (end + 15u) / 16u;
-                for (uint32_t q = tid; q < nq; q += blockDim.x) {
+                // copy-out: whole 16-B blocks inside [beg, end), bytes at the edges
+                uint8_t *gb = (uint8_t *)(ga - a0);
+                const uint32_t beg = a0 + from, end = beg + keep, nq = (end + 15u) / 16u;
+                for (uint32_t q = beg / 16u + tid; q < nq; q += blockDim.x) {
                     const uint32_t lo = 16u * q;
-                    if (lo >= a0 && lo + 16u <= end) {
+                    if (lo >= beg && lo + 16u <= end) {
                         *(u32x4 *)(gb + lo) = *(const u32x4 *)(stg + lo);
                     } else {
-                        const uint32_t q0 = lo > a0 ? lo : a0, q1 = lo + 16u < end ? lo + 16u : end;
+                        const uint32_t q0 = lo > beg ? lo : beg, q1 = lo + 16u < end ? lo + 16u : end;
                         for (uint32_t p = q0; p < q1; p++) gb[p] = stg[p];
                     }
                 }
+                got += keep;
             }
             base += tot;
             carry = carry_next;
+            if (win && hb_window_done(base, skip, cap)) break;   // the window is full: no later round is loaded or walked
         }
         if (tid == 0) {
-            res[idx].len = base;
-            res[idx].status = fail ? HH_ERR_INTERNAL : base > cap ? HH_ERR_CAPACITY : HH_OK;
+            res[idx].len = win ? got : base;
+            res[idx].status = fail ? HH_ERR_INTERNAL
+                              : win ? (got < cap ? HH_ERR_FORMAT : HH_OK) : base > cap ? HH_ERR_CAPACITY : HH_OK;
         }
     }
 }
@@ -296,7 +315,7 @@ int batch_decode(BatchDev *b, const FsmDev *fd, hipEvent_t *ev, const void *d_da
     uint64_t regions = 0;
     for (uint64_t k = 0; k < n; k++) {
         const hh_batch_item &s = items[ord[k]];
-        hd[k] = BatchDesc{s.data_off, s.bits, s.out_off, s.cap, ord[k]};
+        hd[k] = BatchDesc{s.data_off, s.bits, s.out_off, s.cap, ord[k], 0, 0, 0};
         regions += (s.bits + fd->S - 1) / fd->S;
         hr[k].len = 0;
         hr[k].status = HB_UNTOUCHED;
@@ -364,6 +383,43 @@ int batch_decode_items(BatchDev *b, const FsmDev *fd, const void *d_data, uint64
         if (hipGetLastError() != hipSuccess) rc = HH_ERR_DEVICE;
     }
     if (rc == HH_OK) rc = batch_results_enqueue(dr, key, (uint32_t)n, d_out_len, d_status, d_summary, ctl, st);
+    // (also after a failed launch: what was enqueued before it uses the workspace)
+    FS_OK(hipEventRecord(b->end, st));
+    b->pend = 1;
+    b->pend_st = st;
+    return rc;
+}
+
+// Range reads: the workspace and the grids are sized by the piece budget P,
+// which the host knows; how many of the P slots hold a piece is device data.
+// The slots past the pieces hold the empty descriptor (no round walked) and
+// sort to the list's end (bin 0), so k_plan_place and k_batch run with n = P.
+int batch_decode_read(BatchDev *b, const FsmDev *fd, const void *d_data, uint64_t data_bytes,
+                      const hh_batch_item *d_index, uint64_t n_syms, uint64_t block_syms, const hh_block_read *d_reads,
+                      uint64_t m, uint32_t P, void *d_out, uint64_t out_bytes, uint64_t *d_read_len,
+                      int32_t *d_status, hh_batch_summary *d_summary, hipStream_t st) {
+    if (!b->ok) return HH_ERR_UNSUPPORTED;
+    const int grc = batch_grid(b);
+    if (grc != HH_OK) return grc;
+    if (!b->end) FS_OK(hipEventCreateWithFlags(&b->end, hipEventDisableTiming));
+    const int wrc = batch_ws(b, read_ws_bytes(m, P), 0);
+    if (wrc != HH_OK) return wrc;
+    ReadWs w;
+    read_ws_carve(&w, b->d_ws, m, P);
+    if (b->pend && b->pend_st != st) FS_OK(hipStreamWaitEvent(st, b->end, 0));
+    const uint64_t RB = (uint64_t)HB_NR * b->W * fd->S;
+    int rc = read_plan_enqueue(&w, d_index, data_bytes, n_syms, block_syms, d_reads, (uint32_t)m, P, out_bytes, RB,
+                               d_summary, st);
+    if (rc == HH_OK) rc = batch_place_enqueue(w.tmp, w.key, P, w.ctl, w.desc, st);
+    if (rc == HH_OK) {
+        const BatchGeo geo = batch_geo(b, fd, P);
+        const FsmTab tab = {fd->ct, fd->b1, fd->tsym, fd->et, fd->er};
+        const uint32_t grid = P < b->grid_max ? P : b->grid_max;
+        hipLaunchKernelGGL(k_batch, dim3(grid), dim3(64 * b->W), b->lds, st, (const uint8_t *)d_data,
+                           (const BatchDesc *)w.desc, w.res, (uint8_t *)d_out, tab, geo);
+        if (hipGetLastError() != hipSuccess) rc = HH_ERR_DEVICE;
+    }
+    if (rc == HH_OK) rc = read_results_enqueue(&w, (uint32_t)m, P, d_read_len, d_status, d_summary, st);
     // (also after a failed launch: what was enqueued before it uses the workspace)
     FS_OK(hipEventRecord(b->end, st));
     b->pend = 1;

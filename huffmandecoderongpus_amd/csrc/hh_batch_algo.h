@@ -27,6 +27,10 @@
  *           bytes [base, base + n) those below the stream's capacity are
  *           copied out (hb_clip) -- the count goes on past the capacity,
  *           out_len is the stream's full symbol count.
+ *   window  a piece of a range read wants the stream's bytes [skip, skip +
+ *           cap) only (hb_window): rounds before the window are counted, not
+ *           emitted, and the piece ends with the round that fills the window
+ *           (hb_window_done); its length is the bytes delivered.
  *
  * The stream's last region (the one `bits` ends in: hb_span's at_end) takes
  * whole K-bit steps while they fit, the rest bit by bit (b1), and the tail
@@ -165,6 +169,28 @@ HH_FD uint32_t hb_clip(uint64_t base, uint32_t n, uint64_t cap) {
     if (base >= cap) return 0u;
     return cap - base < n ? (uint32_t)(cap - base) : n;
 }
+
+/* The same for a window [skip, skip + cap) of the stream's output (a piece of
+ * hh_decode_blocks_read: hh_batch_read_algo.h): how many of the round's n
+ * bytes at offset base fall into it, *from the offset of the first of them
+ * inside the round (0 when there is none).  No sum is formed: base + n and
+ * skip + cap may lie past 2^64.  With skip = 0 it is hb_clip, *from 0. */
+HH_FD uint32_t hb_window(uint64_t base, uint32_t n, uint64_t skip, uint64_t cap, uint32_t *from) {
+    *from = 0;
+    if (cap == 0) return 0u;
+    if (base >= skip) {
+        const uint64_t d = base - skip;
+        if (d >= cap) return 0u;
+        return cap - d < n ? (uint32_t)(cap - d) : n;
+    }
+    const uint64_t f = skip - base;
+    if (f >= n) return 0u;
+    *from = (uint32_t)f;
+    return cap < n - (uint32_t)f ? (uint32_t)cap : n - (uint32_t)f;
+}
+/* A window piece's last round: the one after which the window is full
+ * (seen = base + the round's bytes; skip + cap <= the stream's symbols). */
+HH_FD int hb_window_done(uint64_t seen, uint64_t skip, uint64_t cap) { return seen >= skip && seen - skip >= cap; }
 
 /* LDS of a workgroup of W waves beside the tables (tabb bytes): per tile the
  * payload rows (SW words + a pad word against bank conflicts when SW is

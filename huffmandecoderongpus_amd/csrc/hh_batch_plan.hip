@@ -45,11 +45,12 @@
 #include "hh_fsm_kern.h"
 
 #define HBP_TB 256u                  // threads per workgroup of the three kernels
-#define HBP_CNT 0u                   // ctl (u32 words): cnt[HBP_BINS]
-#define HBP_CUR HBP_BINS             //                  cur[HBP_BINS]
-#define HBP_DONE (2u * HBP_BINS)     //                  done
+#define HBP_CNT HB_CTL_CNT           // ctl (u32 words): cnt[HBP_BINS]
+#define HBP_CUR HB_CTL_CUR           //                  cur[HBP_BINS]
+#define HBP_DONE HB_CTL_DONE         //                  done
+static_assert(HBP_CUR == HBP_BINS && HBP_DONE == 2u * HBP_BINS, "ctl's layout (hh_batch.h) is for HBP_BINS bins");
 static_assert((HBP_DONE + 1u) * 4u <= HB_PLAN_CTL_BYTES, "the plan's counters fit their block");
-static_assert(sizeof(hh_batch_item) == 32 && sizeof(BatchDesc) == 40 && sizeof(BatchRes) == 16 &&
+static_assert(sizeof(hh_batch_item) == 32 && sizeof(BatchDesc) == 56 && sizeof(BatchRes) == 16 &&
               sizeof(hh_batch_summary) == 24, "layouts the kernels assume");
 
 __global__ __launch_bounds__(HBP_TB) void k_plan_count(const hh_batch_item *__restrict__ items, uint32_t n,
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(HBP_TB) void k_plan_count(const hh_batch_item *__re
         const uint32_t k = hbp_key(it.data_off, it.bits, it.out_off, it.cap, data_bytes, out_bytes, RB);
         const bool ok = !(k & HBP_INVALID);
         // an invalid item's offsets are never copied: they must not become addresses
-        tmp[i] = ok ? BatchDesc{it.data_off, it.bits, it.out_off, it.cap, i} : BatchDesc{0, 0, 0, 0, i};
+        tmp[i] = ok ? BatchDesc{it.data_off, it.bits, it.out_off, it.cap, i, 0, 0, 0} : BatchDesc{0, 0, 0, 0, i, 0, 0, 0};
         key[i] = (uint8_t)k;
         res[i] = BatchRes{0, HB_UNTOUCHED};
         atomicAdd(&s_cnt[k & (HBP_BINS - 1u)], 1u);
@@ -169,8 +170,13 @@ int batch_plan_enqueue(const hh_batch_item *d_items, uint32_t n, uint64_t data_b
     hipLaunchKernelGGL(k_plan_count, dim3(grid), dim3(HBP_TB), 0, st, d_items, n, data_bytes, out_bytes, round_bits,
                        tmp, key, res, ctl, d_summary);
     FS_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_place, dim3(grid), dim3(HBP_TB), 0, st, (const BatchDesc *)tmp, (const uint8_t *)key, n,
-                       ctl, desc);
+    return batch_place_enqueue(tmp, key, n, ctl, desc, st);
+}
+
+int batch_place_enqueue(const BatchDesc *tmp, const uint8_t *key, uint32_t n, uint32_t *ctl, BatchDesc *desc,
+                        hipStream_t st) {
+    const uint32_t grid = (uint32_t)(((uint64_t)n + HBP_TB - 1u) / HBP_TB);
+    hipLaunchKernelGGL(k_plan_place, dim3(grid), dim3(HBP_TB), 0, st, tmp, key, n, ctl, desc);
     FS_OK(hipGetLastError());
     return HH_OK;
 }

@@ -422,6 +422,72 @@ int hh_decode_batch_device_items(hh_decoder *dec, const void *d_data, uint64_t d
                                  hh_batch_summary *d_summary /* device, may be NULL */,
                                  void *hip_stream);
 
+/* Random access into a block-coded buffer: byte ranges of the uncompressed
+ * data, each delivered to a destination of its own, in one stream-ordered
+ * call. */
+typedef struct {
+    uint64_t src_off;   /* first byte of the range in the uncompressed data */
+    uint64_t len;       /* bytes; 0 is allowed                               */
+    uint64_t dst_off;   /* where the bytes go in d_out; any alignment        */
+} hh_block_read;
+
+/* The blocked buffer is what hh_encoder_encode_blocks_items (or
+ * hh_compress_blocks_device_items) leaves behind: n_syms symbols in nb =
+ * ceil(n_syms / block_syms) blocks, block b the symbols [b * block_syms,
+ * min(n_syms, (b + 1) * block_syms)), d_index[b] its item.  Of d_index[b]
+ * only data_off and bits are read; out_off and cap are ignored (the block's
+ * place and size follow from n_syms and block_syms).
+ * Read i delivers the bytes [src_off, src_off + len) of the uncompressed
+ * data to d_out + dst_off: the same bytes as that slice of a full decode.  A
+ * read may cross any number of block edges.  Of each touched block only the
+ * rounds up to the one that holds the read's last byte are walked; nothing
+ * is decoded into a scratch buffer.  Destination ranges of different reads
+ * must not overlap -- the caller's duty, as for hh_decode_batch_device; they
+ * may touch at any alignment (no byte a read does not own is stored, and no
+ * wider store covers a neighbour's byte).
+ * Stream ordered, exactly as hh_decode_batch_device_items: everything is
+ * enqueued on hip_stream; no synchronisation, no device-to-host copy,
+ * nothing on the null stream (but for the wait before the batch workspace
+ * grows, as there); d_reads and d_index are read in stream order by the
+ * plan's kernels only; d_out, d_read_len, d_status and d_summary are
+ * complete when the stream has passed the call's work.  The call shares the
+ * decoder's batch workspace and its end event: hh_decoder_set_tree,
+ * hh_decoder_destroy, hh_decode_batch_device and a batch on another stream
+ * behave towards it as towards an items batch.  hh_stats after the call: all
+ * zero but state_machine = 3.
+ * Checked on the host, before anything is enqueued: HH_ERR_ARG for a null
+ * pointer with m > 0 (d_summary excepted; d_index only when n_syms > 0),
+ * block_syms == 0, d_data off a 4-byte boundary, no tree set;
+ * HH_ERR_UNSUPPORTED for a tree the batch cannot take, or a piece budget
+ * P = out_bytes / block_syms + 2 m of 2^32 - 1 or more (reads with disjoint
+ * destinations never have more pieces than P; the workspace is sized by it:
+ * 133 P + 52 m bytes and some).  m == 0 returns HH_OK, sets a d_summary
+ * given to the empty summary and enqueues nothing else.
+ * Checked on the device, per read, overflow-safe: src_off + len <= n_syms,
+ * dst_off + len <= out_bytes; for every block the read touches, the index
+ * entry's payload rules (data_off a multiple of 4; for bits > 0, data_off +
+ * ceil(bits/8) + HH_PAYLOAD_PAD <= data_bytes).
+ * d_status[i]: HH_OK, d_read_len[i] == len.  HH_ERR_ARG: the read is out of
+ * range (it gets no piece: not a byte is read or written for it, d_read_len
+ * [i] = 0); or a touched index entry breaks a rule (that block's part is
+ * neither read nor written, the read's other parts may be); or the reads'
+ * pieces exceed P (overlapping destinations only).  HH_ERR_FORMAT: a block's
+ * stream ended before its part of the read was filled -- index and data
+ * disagree; d_read_len[i] is the number of bytes delivered.
+ * HH_ERR_INTERNAL: as in the items call.  A failing read's status is that of
+ * its lowest-numbered failing block.  In every case nothing outside
+ * [dst_off, dst_off + len) is written and the other reads are undisturbed.
+ * d_summary: total_len the delivered bytes of the HH_OK reads, n_failed,
+ * first_failed, first_status over the reads. */
+int hh_decode_blocks_read(hh_decoder *dec, const void *d_data, uint64_t data_bytes,
+                          const hh_batch_item *d_index /* device, nb */,
+                          uint64_t n_syms, uint64_t block_syms,
+                          const hh_block_read *d_reads /* device, m */, uint64_t m,
+                          void *d_out, uint64_t out_bytes,
+                          uint64_t *d_read_len /* device, m */, int32_t *d_status /* device, m */,
+                          hh_batch_summary *d_summary /* device, may be NULL */,
+                          void *hip_stream);
+
 /* ---------------------------------------------------------------------- */
 /* Blocked encode: the producer of a batch.  n symbols are cut into       */
 /* nb = ceil(n / block_syms) blocks, block b the symbols                  */

@@ -174,6 +174,7 @@ _SIGS = {
     "hipHuffApproach": ([C.c_void_p, C.c_void_p, C.c_void_p], None),
     "hh_debug_counters": ([C.c_void_p, C.c_void_p], C.c_int),
     "hh_debug_fsm": ([C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hh_debug_geometry": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
 }
 
 
@@ -826,6 +827,15 @@ class Decoder:
         w = C.c_uint32(0)
         _check(lib().hh_decode_batch_round_tiles(self._h, C.byref(w)), "batch_round_tiles")
         return int(w.value)
+
+    def geometry(self) -> dict:
+        """hh_debug_geometry: what set_tree chose for the batched decode --
+        region bits S, emission step K, remainder step r, count step bits cb,
+        the batch's head G, its tiles per round W, the states ns and
+        k_batch's LDS bytes."""
+        g = (C.c_uint32 * 8)()
+        _check(lib().hh_debug_geometry(self._h, g), "geometry")
+        return dict(zip(("S", "K", "r", "cb", "G", "W", "ns", "lds"), (int(v) for v in g)))
 
     def tile_bits(self) -> int:
         """Bits per tile for the current tree (segments are whole tiles)."""

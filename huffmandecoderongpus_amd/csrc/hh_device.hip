@@ -657,3 +657,21 @@ extern "C" int hh_debug_fsm(hh_decoder *d, uint64_t ntiles, uint32_t *rec, uint3
     HIP_OK(hipSetDevice(d->device));
     return fsm_debug_arrays(&d->fsm_ws, ntiles, rec, fx, tsum, xs);
 }
+
+// Diagnostic: the geometry hh_decoder_set_tree chose for the batched decode:
+// region bits S, emission step K, remainder step r, count step bits cb, the
+// batch's head G, its waves per round W, the states ns, k_batch's LDS bytes.
+// Host fields only: no device call.
+extern "C" int hh_debug_geometry(hh_decoder *d, uint32_t out[8]) {
+    if (!d || !out || !d->have_tree) return HH_ERR_ARG;
+    if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;
+    out[0] = d->fsm.S;
+    out[1] = d->fsm.K;
+    out[2] = d->fsm.r;
+    out[3] = d->fsm.cb;
+    out[4] = d->batch.G;
+    out[5] = d->batch.W;
+    out[6] = d->fsm.ns;
+    out[7] = d->batch.lds;
+    return HH_OK;
+}

@@ -147,6 +147,9 @@ _SIGS = {
     "hh_decode_blocks_read": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                               C.c_int),
+    "hh_decode_blocks_gather": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                 C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                                C.c_int),
     "hh_decode_batch_round_tiles": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     "hh_decoder_tile_bits": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hh_decode_device_range": ([C.c_void_p, C.c_void_p, C.POINTER(_Range), C.c_void_p,
@@ -770,6 +773,23 @@ class Decoder:
         (read_len the bytes delivered), and the others are served; only what
         the host can check raises.  The tensors are kept alive until the
         next batch call on this decoder or close()."""
+        return self._blocks_call("hh_decode_blocks_read", "read_blocks", data, index, n_syms, block_syms, reads, out,
+                                 read_len, status, summary, stream, data_bytes, out_bytes)
+
+    def gather_blocks(self, data, index, n_syms: int, block_syms: int, reads, out, read_len=None, status=None,
+                      summary=False, stream=None, data_bytes: Optional[int] = None,
+                      out_bytes: Optional[int] = None) -> tuple:
+        """hh_decode_blocks_gather: read_blocks with every touched block
+        walked once per call for all the reads that fall into it -- the call
+        for dense small reads (several per block).  Parameters, results,
+        statuses and stream order are read_blocks'; the number of blocks must
+        be below 2^32 - 1 (the call keeps a few words per block and scans
+        them on every call)."""
+        return self._blocks_call("hh_decode_blocks_gather", "gather_blocks", data, index, n_syms, block_syms, reads,
+                                 out, read_len, status, summary, stream, data_bytes, out_bytes)
+
+    def _blocks_call(self, fn, what, data, index, n_syms, block_syms, reads, out, read_len, status, summary, stream,
+                     data_bytes, out_bytes) -> tuple:
         import torch
         assert data.is_cuda and out.is_cuda and data.dtype == torch.uint8 and out.dtype == torch.uint8
         assert data.is_contiguous() and out.is_contiguous()
@@ -803,13 +823,13 @@ class Decoder:
         assert read_len.is_cuda and read_len.dtype == torch.int64 and read_len.is_contiguous() and read_len.numel() == m
         assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == m
         self._batch_keep = (data, index, reads, out, read_len, status, summ)
-        rc = lib().hh_decode_blocks_read(
+        rc = getattr(lib(), fn)(
             self._h, data.data_ptr(), data.numel() if data_bytes is None else data_bytes,
             index.data_ptr() if nb else None, n_syms, block_syms, reads.data_ptr() if m else None, m,
             out.data_ptr(), out.numel() if out_bytes is None else out_bytes,
             read_len.data_ptr() if m else None, status.data_ptr() if m else None,
             summ.data_ptr() if summ is not None else None, s.cuda_stream)
-        _check(rc, "read_blocks")
+        _check(rc, what)
         return (read_len, status, summ) if summ is not None else (read_len, status)
 
     @staticmethod

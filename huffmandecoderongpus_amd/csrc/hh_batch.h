@@ -44,12 +44,52 @@ struct BatchDev {
     hipStream_t pend_st;     // its stream
 };
 
+// What a round's kernels share (k_batch, hh_batch.hip; k_gather,
+// hh_batch_gather.hip): the LDS they may use, the round's geometry and the
+// emission sink.
+#define HB_LDS (160u * 1024u)
+
+struct BatchGeo {
+    uint32_t ns, K, r, S, G, W;
+    uint32_t pay_off, misc_off, stg_off, stg_bytes;   // LDS byte offsets / the staging's size
+    uint32_t n;
+};
+
+// The emission sink: a step's symbols shifted into the current dword, which
+// is stored to its aligned staging address once its last byte is there (the
+// bytes of earlier runs in it zero); a run that ends inside a dword ORs its
+// bytes in after every run's stores (k_emf's scheme, hh_fsm.hip).
+struct BatchSink {
+    uint8_t *lds;
+    uint32_t wd, sh, a;
+    __device__ __forceinline__ void init(uint8_t *smem, uint32_t oa) {
+        lds = smem;
+        wd = oa & ~3u;
+        sh = (oa & 3u) * 8u;
+        a = 0;
+    }
+    __host__ __device__ __forceinline__ void put(uint64_t e) {
+        const uint32_t lo = (uint32_t)e, u = sh + ((uint32_t)(e >> 32) & 255u);
+        const uint64_t t = (uint64_t)lo << sh;
+        const uint32_t an = (uint32_t)t | a;
+        const bool full = u >= 32u;
+        if (full) *(uint32_t *)(lds + wd) = an;
+        a = full ? (uint32_t)(t >> 32) : an;
+        wd += full ? 4u : 0u;
+        sh = u & 31u;
+    }
+};
+
 // After the tree's tables are uploaded (fd->ok): the round's shape.
 void batch_setup(BatchDev *b, const FsmDev *fd, uint32_t G, uint32_t minlen);
 void batch_free(BatchDev *b);
 // The host waits for a pending batch of device items (the tables and the
 // workspace it uses are about to change).
 int batch_wait(BatchDev *b);
+// The workspace grown to need_d device and need_h pinned host bytes; the
+// geometry of a launch over n list entries.
+int batch_ws(BatchDev *b, size_t need_d, size_t need_h);
+BatchGeo batch_geo(const BatchDev *b, const FsmDev *fd, uint64_t n);
 // One launch for items[0..n) (validated by the caller), enqueued on st;
 // returns when done: out_len[i], status[i] (may be NULL); *ms the launch's
 // device time (events ev[0], ev[1]), *lanes the regions of all streams.
@@ -85,6 +125,8 @@ int batch_decode_read(BatchDev *b, const FsmDev *fd, const void *d_data, uint64_
 #define HB_CTL_DONE 128u
 #define HB_CTL_TOTAL 130u
 #define HB_CTL_FIRST 132u
+// for gathered reads (hh_batch_gather.hip): the walks, i.e. the touched blocks
+#define HB_CTL_WALKS 134u
 int batch_plan_enqueue(const hh_batch_item *d_items, uint32_t n, uint64_t data_bytes, uint64_t out_bytes,
                        uint64_t round_bits, BatchDesc *desc, BatchRes *res, BatchDesc *tmp, uint8_t *key,
                        uint32_t *ctl, hh_batch_summary *d_summary, hipStream_t st);
@@ -121,5 +163,19 @@ int read_plan_enqueue(const ReadWs *w, const hh_batch_item *d_index, uint64_t da
                       uint64_t round_bits, hh_batch_summary *d_summary, hipStream_t st);
 int read_results_enqueue(const ReadWs *w, uint32_t m, uint32_t P, uint64_t *d_read_len, int32_t *d_status,
                          hh_batch_summary *d_summary, hipStream_t st);
+// The plan's first half alone (the counters cleared, k_read_count,
+// k_read_scan): validity, first slots, the slots that hold a piece.
+int read_count_enqueue(const ReadWs *w, uint64_t n_syms, uint64_t block_syms, const hh_block_read *d_reads,
+                       uint32_t m, uint32_t P, uint64_t out_bytes, hh_batch_summary *d_summary, hipStream_t st);
+
+// hh_batch_gather.hip: gathered range reads (hh_decode_blocks_gather) -- the
+// plan of hh_decode_blocks_read up to the pieces, the pieces grouped by block
+// and k_gather, which walks every touched block once for all its pieces.
+// nb: the blocks of the buffer (< 2^32 - 1, hbg_blocks).
+int batch_decode_gather(BatchDev *b, const FsmDev *fd, const void *d_data, uint64_t data_bytes,
+                        const hh_batch_item *d_index, uint64_t n_syms, uint64_t block_syms,
+                        const hh_block_read *d_reads, uint64_t m, uint32_t P, uint32_t nb, void *d_out,
+                        uint64_t out_bytes, uint64_t *d_read_len, int32_t *d_status, hh_batch_summary *d_summary,
+                        hipStream_t st);
 
 #endif

@@ -42,39 +42,6 @@
 #include "hh_batch_algo.h"
 #include "hh_fsm_kern.h"
 
-#define HB_LDS (160u * 1024u)
-
-struct BatchGeo {
-    uint32_t ns, K, r, S, G, W;
-    uint32_t pay_off, misc_off, stg_off, stg_bytes;   // LDS byte offsets / the staging's size
-    uint32_t n;
-};
-
-// The emission sink: a step's symbols shifted into the current dword, which
-// is stored to its aligned staging address once its last byte is there (the
-// bytes of earlier runs in it zero); a run that ends inside a dword ORs its
-// bytes in after every run's stores (k_emf's scheme, hh_fsm.hip).
-struct BatchSink {
-    uint8_t *lds;
-    uint32_t wd, sh, a;
-    __device__ __forceinline__ void init(uint8_t *smem, uint32_t oa) {
-        lds = smem;
-        wd = oa & ~3u;
-        sh = (oa & 3u) * 8u;
-        a = 0;
-    }
-    __host__ __device__ __forceinline__ void put(uint64_t e) {
-        const uint32_t lo = (uint32_t)e, u = sh + ((uint32_t)(e >> 32) & 255u);
-        const uint64_t t = (uint64_t)lo << sh;
-        const uint32_t an = (uint32_t)t | a;
-        const bool full = u >= 32u;
-        if (full) *(uint32_t *)(lds + wd) = an;
-        a = full ? (uint32_t)(t >> 32) : an;
-        wd += full ? 4u : 0u;
-        sh = u & 31u;
-    }
-};
-
 __global__ __launch_bounds__(64 * HB_WMAX) void k_batch(const uint8_t *__restrict__ data,
                                                         const BatchDesc *__restrict__ desc, BatchRes *__restrict__ res,
                                                         uint8_t *__restrict__ out, FsmTab tab, BatchGeo geo) {
@@ -242,7 +209,7 @@ void batch_free(BatchDev *b) {
 
 // The workspace: need_d device bytes, need_h pinned host bytes (the device
 // items' batch keeps nothing on the host).
-static int batch_ws(BatchDev *b, size_t need_d, size_t need_h) {
+int batch_ws(BatchDev *b, size_t need_d, size_t need_h) {
     if (b->d_size < need_d) {
         // (a synchronous call has returned, and a pending asynchronous decode
         // does not use this workspace; a batch of device items may still run)
@@ -283,7 +250,7 @@ static int batch_grid(BatchDev *b) {
     return HH_OK;
 }
 
-static BatchGeo batch_geo(const BatchDev *b, const FsmDev *fd, uint64_t n) {
+BatchGeo batch_geo(const BatchDev *b, const FsmDev *fd, uint64_t n) {
     BatchGeo geo;
     geo.ns = fd->ns; geo.K = fd->K; geo.r = fd->r; geo.S = fd->S; geo.G = b->G; geo.W = b->W;
     geo.pay_off = emf_tab_bytes(fd->ns, fd->K, fd->r);

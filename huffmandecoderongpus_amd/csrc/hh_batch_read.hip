@@ -258,18 +258,26 @@ void read_ws_carve(ReadWs *w, void *d_ws, uint64_t m, uint32_t P) {
     w->key = p;
 }
 
-int read_plan_enqueue(const ReadWs *w, const hh_batch_item *d_index, uint64_t data_bytes, uint64_t n_syms,
-                      uint64_t block_syms, const hh_block_read *d_reads, uint32_t m, uint32_t P, uint64_t out_bytes,
-                      uint64_t round_bits, hh_batch_summary *d_summary, hipStream_t st) {
-    if (m == 0 || P == 0 || block_syms == 0 || round_bits == 0) return HH_ERR_INTERNAL;
+int read_count_enqueue(const ReadWs *w, uint64_t n_syms, uint64_t block_syms, const hh_block_read *d_reads,
+                       uint32_t m, uint32_t P, uint64_t out_bytes, hh_batch_summary *d_summary, hipStream_t st) {
+    if (m == 0 || P == 0 || block_syms == 0) return HH_ERR_INTERNAL;
     const uint32_t gm = (uint32_t)(((uint64_t)m + HBR_TB - 1u) / HBR_TB);
-    const uint32_t gp = (uint32_t)(((uint64_t)P + HBR_TB - 1u) / HBR_TB);
     FS_OK(hipMemsetAsync(w->ctl, 0, HB_PLAN_CTL_BYTES, st));
     hipLaunchKernelGGL(k_read_count, dim3(gm), dim3(HBR_TB), 0, st, d_reads, m, n_syms, out_bytes, block_syms,
                        w->start, w->reads, w->rec, w->rstat, w->ctl, d_summary);
     FS_OK(hipGetLastError());
     hipLaunchKernelGGL(k_read_scan, dim3(1), dim3(HBR_SCAN_TB), 0, st, w->start, m, (uint64_t)P, w->rstat, w->ctl);
     FS_OK(hipGetLastError());
+    return HH_OK;
+}
+
+int read_plan_enqueue(const ReadWs *w, const hh_batch_item *d_index, uint64_t data_bytes, uint64_t n_syms,
+                      uint64_t block_syms, const hh_block_read *d_reads, uint32_t m, uint32_t P, uint64_t out_bytes,
+                      uint64_t round_bits, hh_batch_summary *d_summary, hipStream_t st) {
+    if (round_bits == 0) return HH_ERR_INTERNAL;
+    const int rc = read_count_enqueue(w, n_syms, block_syms, d_reads, m, P, out_bytes, d_summary, st);
+    if (rc != HH_OK) return rc;
+    const uint32_t gp = (uint32_t)(((uint64_t)P + HBR_TB - 1u) / HBR_TB);
     hipLaunchKernelGGL(k_read_fill, dim3(gp), dim3(HBR_TB), 0, st, P, (const uint64_t *)w->start, m,
                        (const hh_block_read *)w->reads, d_index, data_bytes, block_syms, round_bits, w->tmp, w->key,
                        w->res, w->own, w->ctl);

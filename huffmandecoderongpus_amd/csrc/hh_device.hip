@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "hh_algo.h"
+#include "hh_batch_gather_algo.h"
 #include "hh_batch_read_algo.h"
 #include "hh_dec.h"
 #include "hh_fsm_algo.h"
@@ -554,6 +555,35 @@ extern "C" int hh_decode_blocks_read(hh_decoder *d, const void *d_data, uint64_t
     const int rc = batch_decode_read(&d->batch, &d->fsm, d_data, data_bytes, d_index, n_syms, block_syms, d_reads, m,
                                      (uint32_t)P, d_out, out_bytes, d_read_len, d_status, d_summary,
                                      (hipStream_t)hip_stream);
+    if (rc != HH_OK) return rc;
+    memset(&d->stats, 0, sizeof(d->stats));                // (the host knows no lengths)
+    d->stats.state_machine = 3;
+    return HH_OK;
+}
+
+// Gathered range reads: hh_decode_blocks_read's checks, and the blocks must
+// number below 2^32 - 1 (a few words per block are kept; before any allocation).
+extern "C" int hh_decode_blocks_gather(hh_decoder *d, const void *d_data, uint64_t data_bytes,
+                                       const hh_batch_item *d_index, uint64_t n_syms, uint64_t block_syms,
+                                       const hh_block_read *d_reads, uint64_t m, void *d_out, uint64_t out_bytes,
+                                       uint64_t *d_read_len, int32_t *d_status, hh_batch_summary *d_summary,
+                                       void *hip_stream) {
+    if (!d) return HH_ERR_ARG;
+    if (m == 0) {
+        if (!d_summary) return HH_OK;
+        HIP_OK(hipSetDevice(d->device));
+        return batch_summary_clear(d_summary, (hipStream_t)hip_stream);
+    }
+    if (!d_reads || !d_read_len || !d_status || !d_data || !d_out || !d->have_tree) return HH_ERR_ARG;
+    if ((!d_index && n_syms > 0) || block_syms == 0) return HH_ERR_ARG;
+    if (((uintptr_t)d_data & 3u) != 0) return HH_ERR_ARG;   // word loads
+    if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;
+    uint64_t P = 0, nb = 0;
+    if (!hbr_budget(out_bytes, block_syms, m, &P) || !hbg_blocks(n_syms, block_syms, &nb)) return HH_ERR_UNSUPPORTED;
+    HIP_OK(hipSetDevice(d->device));
+    const int rc = batch_decode_gather(&d->batch, &d->fsm, d_data, data_bytes, d_index, n_syms, block_syms, d_reads, m,
+                                       (uint32_t)P, (uint32_t)nb, d_out, out_bytes, d_read_len, d_status, d_summary,
+                                       (hipStream_t)hip_stream);
     if (rc != HH_OK) return rc;
     memset(&d->stats, 0, sizeof(d->stats));                // (the host knows no lengths)
     d->stats.state_machine = 3;

@@ -488,8 +488,42 @@ int hh_decode_blocks_read(hh_decoder *dec, const void *d_data, uint64_t data_byt
                           hh_batch_summary *d_summary /* device, may be NULL */,
                           void *hip_stream);
 
+/* The same reads with every touched block walked at most once per call,
+ * however many reads fall into it: for dense small reads (records by row
+ * id, pages of a column, a gather), where hh_decode_blocks_read decodes a
+ * block from its root once per read that touches it.
+ * Equal to hh_decode_blocks_read: the arguments and their meaning; for every
+ * input the bytes in d_out, d_read_len, d_status and d_summary (statuses of
+ * out-of-range and empty reads, bad index entries, blocks that end early and
+ * the piece budget P included; the content of overlapping destinations is
+ * unspecified in both calls); the host checks; the stream-order rules (no
+ * synchronisation, no device-to-host copy, nothing on the null stream but
+ * for the wait before the workspace grows); the shared batch workspace and
+ * end event; hh_stats after the call.
+ * Different: one more host check -- nb = ceil(n_syms / block_syms) of 2^32 -
+ * 1 or more is HH_ERR_UNSUPPORTED, before any allocation -- because the call
+ * keeps 20 bytes per block (its pieces' count, list position and cursor, the
+ * end of its last window) and 32 per block that can be touched, min(nb, P),
+ * beside hh_decode_blocks_read's 133 P + 52 m bytes; and every call does
+ * O(nb) work to clear and scan those, whatever the reads.  Of a touched
+ * block the rounds up to the one that holds the last byte any read wants of
+ * it are walked, once; a round in which no read has a byte is counted and
+ * not emitted.
+ * Which to use (measured: DESIGN.md section 13): this call when several
+ * reads may fall into one block; hh_decode_blocks_read when reads are sparse
+ * (at most about one per touched block) or nb is far larger than the number
+ * of reads, where the per-block bookkeeping buys nothing. */
+int hh_decode_blocks_gather(hh_decoder *dec, const void *d_data, uint64_t data_bytes,
+                            const hh_batch_item *d_index /* device, nb */,
+                            uint64_t n_syms, uint64_t block_syms,
+                            const hh_block_read *d_reads /* device, m */, uint64_t m,
+                            void *d_out, uint64_t out_bytes,
+                            uint64_t *d_read_len /* device, m */, int32_t *d_status /* device, m */,
+                            hh_batch_summary *d_summary /* device, may be NULL */,
+                            void *hip_stream);
+
 /* ---------------------------------------------------------------------- */
-/* Blocked encode: the producer of a batch.  n symbols are cut into       */
+/* Blocked encode: the producer of a batch. n symbols are cut into       */
 /* nb = ceil(n / block_syms) blocks, block b the symbols                  */
 /* [b * block_syms, min(n, (b + 1) * block_syms)), and every block is     */
 /* encoded on its own from the root, exactly as hh_encode would encode    */

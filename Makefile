@@ -26,7 +26,7 @@ DEC_UNITS  := hh_device hh_r2 hh_exact hh_host hh_fsm hh_one hh_batch hh_batch_p
 DEC_HDRS   := $(addprefix $(CSRC)/,hh_algo.h hh_batch.h hh_batch_algo.h hh_batch_gather_algo.h hh_batch_plan_algo.h \
               hh_batch_read_algo.h hh_dec.h \
               hh_fsm.h hh_fsm_algo.h hh_fsm_dev.h hh_fsm_kern.h hh_internal.h) include/hiphuff.h
-OTHER_OBJS := $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_build.o \
+OTHER_OBJS := $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_encr.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_build.o \
               $(BUILD)/hh_plugin.o
 
 all: lib cli oracle emu ubench
@@ -57,6 +57,10 @@ $(BUILD)/hh_encb.o: $(CSRC)/hh_encb.hip $(CSRC)/hh_enc_kern.h $(CSRC)/hh_interna
                     include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(BUILD)/hh_encr.o: $(CSRC)/hh_encr.hip $(CSRC)/hh_encr_algo.h $(CSRC)/hh_enc_kern.h $(CSRC)/hh_internal.h \
+                    $(CSRC)/hh_enc.h include/hiphuff.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(BUILD)/hh_hist.o: $(CSRC)/hh_hist.hip $(CSRC)/hh_hist_kern.h $(CSRC)/hh_enc.h include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -66,8 +70,8 @@ $(BUILD)/hh_build.o: $(CSRC)/hh_build.c include/hiphuff.h | $(BUILD)
 $(BUILD)/hh_probe.o: $(CSRC)/hh_probe.hip include/hiphuff.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(DEC_UNITS:%=$(BUILD)/%.o) $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o \
-        $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
+$(LIB): $(DEC_UNITS:%=$(BUILD)/%.o) $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_encr.o $(BUILD)/hh_hist.o \
+        $(BUILD)/hh_probe.o $(BUILD)/hh_huff.o $(BUILD)/hh_build.o $(BUILD)/hh_plugin.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 $(CLI): $(PKG)/host/hh_cli.c $(LIB) include/hiphuff.h include/hiphuff_plugin.h
@@ -87,12 +91,13 @@ $(BUILD)/ub_fetch: tools/ubench/ub_fetch.hip | $(BUILD)
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $<
 
 $(EMU): tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp tests/emu/hh_batch_emu.cpp tests/emu/hh_batch_plan_emu.cpp \
-        tests/emu/hh_blocks_read_emu.cpp tests/emu/hh_blocks_gather_emu.cpp $(CSRC)/hh_algo.h $(CSRC)/hh_fsm_algo.h \
+        tests/emu/hh_blocks_read_emu.cpp tests/emu/hh_blocks_gather_emu.cpp tests/emu/hh_encr_emu.cpp \
+        $(CSRC)/hh_algo.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_encr_algo.h \
         $(CSRC)/hh_batch_algo.h $(CSRC)/hh_batch_gather_algo.h $(CSRC)/hh_batch_plan_algo.h \
         $(CSRC)/hh_batch_read_algo.h $(CSRC)/hh_fsm.h $(CSRC)/hh_internal.h $(BUILD)/hh_huff.o
 	$(CXX) -O2 -fPIC -shared $(INC) -Wno-comment -o $@ tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp \
 	    tests/emu/hh_batch_emu.cpp tests/emu/hh_batch_plan_emu.cpp tests/emu/hh_blocks_read_emu.cpp \
-	    tests/emu/hh_blocks_gather_emu.cpp $(BUILD)/hh_huff.o
+	    tests/emu/hh_blocks_gather_emu.cpp tests/emu/hh_encr_emu.cpp $(BUILD)/hh_huff.o
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(EMU)

@@ -131,6 +131,16 @@ _SIGS = {
     "hh_compress_blocks_device_items": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                          C.POINTER(_TreeBuf), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                          C.c_void_p], C.c_int),
+    "hh_encode_ragged_bound": ([C.POINTER(_Tree), C.c_uint64, C.c_uint64], C.c_uint64),
+    "hh_encode_ragged": ([C.POINTER(_Tree), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                          C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
+    "hh_encoder_encode_ragged": ([C.c_void_p, C.POINTER(_Tree), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p],
+                                 C.c_int),
+    "hh_compress_ragged_bound": ([C.c_uint64, C.c_uint64], C.c_uint64),
+    "hh_compress_ragged_device": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.POINTER(_TreeBuf), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p],
+                                  C.c_int),
     "hh_decoder_create": ([C.POINTER(C.c_void_p), C.POINTER(_Config)], C.c_int),
     "hh_decoder_destroy": ([C.c_void_p], None),
     "hh_decoder_set_tree": ([C.c_void_p, C.POINTER(_Tree)], C.c_int),
@@ -346,6 +356,56 @@ class Tree:
         _check(rc, "encode_blocks")
         return out[: total.value + PAYLOAD_PAD].copy(), items
 
+    def encode_ragged(self, syms: np.ndarray, offsets, cap: Optional[int] = None) -> tuple:
+        """The host reference of the ragged blocked encode (hh_encode_ragged):
+        record r the symbols [offsets[r], offsets[r + 1]) (offsets[0] == 0,
+        nondecreasing, offsets[-1] == len(syms); a record may be empty), each
+        encoded on its own and packed at 4-byte boundaries -> (data +
+        PAYLOAD_PAD zero bytes, items (nrec, 4) uint64: data_off, bits,
+        out_off, cap).  cap: the output's capacity (default:
+        encode_ragged_bound); a HipHuffError of status -5 carries .items and
+        .total_bytes."""
+        syms = np.ascontiguousarray(syms, np.uint8)
+        offs = _ragged_offsets(offsets)
+        n, nrec = len(syms), offs.size - 1
+        if cap is None:
+            cap = encode_ragged_bound(self, n, nrec)
+        out = np.zeros(cap + PAYLOAD_PAD, np.uint8)
+        items = np.zeros((nrec, 4), np.uint64)
+        total = C.c_uint64(0)
+        rc = lib().hh_encode_ragged(C.byref(self._c), syms.ctypes.data, n, offs.ctypes.data, nrec, out.ctypes.data, cap,
+                                    items.ctypes.data, C.byref(total))
+        if rc == -5:
+            e = HipHuffError(rc, "encode_ragged")
+            e.items, e.total_bytes = items, int(total.value)
+            raise e
+        _check(rc, "encode_ragged")
+        return out[: total.value + PAYLOAD_PAD].copy(), items
+
+
+def _ragged_offsets(offsets) -> np.ndarray:
+    """A host offsets list as the uint64 (nrec + 1,) array the C calls take."""
+    offs = np.ascontiguousarray(offsets)
+    if offs.ndim != 1 or offs.size < 1 or offs.dtype.kind not in "ui":
+        raise ValueError("offsets: a vector of nrec + 1 integers")
+    return offs.astype(np.int64, copy=False).view(np.uint64) if offs.dtype.kind == "i" else \
+        np.ascontiguousarray(offs, np.uint64)
+
+
+def encode_ragged_bound(tree: "Tree", n: int, nrec: int) -> int:
+    """hh_encode_ragged_bound: bytes that always hold the ragged stream of n
+    symbols of tree in nrec records."""
+    bound = int(lib().hh_encode_ragged_bound(C.byref(tree._c), n, nrec))
+    if bound == 0 and (n or nrec):
+        raise HipHuffError(-4, "encode_ragged bound")
+    return bound
+
+
+def compress_ragged_bound(n: int, nrec: int) -> int:
+    """hh_compress_ragged_bound: bytes that always hold n symbols compressed
+    in nrec records with their own Huffman code."""
+    return int(lib().hh_compress_ragged_bound(n, nrec))
+
 
 def _nblocks(n: int, block_syms: int) -> int:
     return -(-n // block_syms) if block_syms > 0 else 0
@@ -503,6 +563,79 @@ class Encoder:
             e.tree, e.items, e.total_bytes = Tree._from_buf(tb), items, int(total.value)
             raise e
         _check(rc, "compress_blocks")
+        return Tree._from_buf(tb), items, int(total.value)
+
+    @staticmethod
+    def _ragged_offsets_dev(offsets, device, s):
+        """offsets as a contiguous CUDA int64 (nrec + 1,) tensor; a host
+        array is uploaded on the call's stream s."""
+        import torch
+        if not torch.is_tensor(offsets):
+            h = _ragged_offsets(offsets).view(np.int64)
+            with torch.cuda.stream(s):
+                offsets = torch.from_numpy(h).to(device, non_blocking=True)
+        if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.dim() == 1
+                and offsets.numel() >= 1):
+            raise ValueError("offsets: a contiguous CUDA int64 tensor of nrec + 1 values")
+        return offsets
+
+    def encode_ragged(self, tree: "Tree", syms, offsets, out, stream=None, items_out=None,
+                      host_items: bool = True) -> tuple:
+        """hh_encoder_encode_ragged: syms cut into records at offsets (a CUDA
+        int64 (nrec + 1,) tensor: 0 first, nondecreasing, syms.numel() last; a
+        host array is uploaded on the call's stream), every record its own
+        stream from the root, packed into out at 4-byte boundaries in one
+        call (syms, out: torch uint8 CUDA tensors; out holds
+        encode_ragged_bound(tree, n, nrec) bytes, plus PAYLOAD_PAD for a
+        decode).  Returns (items, total_bytes): items an (nrec, 4) uint64
+        array of (data_off, bits, out_off, cap) rows for Decoder.decode_batch,
+        or None with host_items=False (nothing per record crosses to the
+        host).  items_out: an int64 (nrec, 4) CUDA tensor that receives the
+        rows on the device, for Decoder.decode_batch_items.  A HipHuffError
+        of status -5 (capacity) carries .items and .total_bytes."""
+        import torch
+        assert syms.is_cuda and out.is_cuda and syms.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert syms.is_contiguous() and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(syms.device)
+        offsets = self._ragged_offsets_dev(offsets, syms.device, s)
+        n, nrec = syms.numel(), offsets.numel() - 1
+        items = np.zeros((nrec, 4), np.uint64) if host_items else None
+        total = C.c_uint64(0)
+        rc = lib().hh_encoder_encode_ragged(
+            self._h, C.byref(tree._c), syms.data_ptr() if n else None, n, offsets.data_ptr(), nrec, out.data_ptr(),
+            out.numel(), self._items_out_ptr(items_out, nrec) if items_out is not None else None,
+            items.ctypes.data if host_items and nrec else None, C.byref(total), s.cuda_stream)
+        if rc == -5:
+            e = HipHuffError(rc, "encoder_encode_ragged")
+            e.items, e.total_bytes = items, int(total.value)
+            raise e
+        _check(rc, "encoder_encode_ragged")
+        return items, int(total.value)
+
+    def compress_ragged(self, syms, offsets, out, stream=None, items_out=None, host_items: bool = True) -> tuple:
+        """hh_compress_ragged_device: histogram, one tree for all records,
+        then encode_ragged with it (out holds compress_ragged_bound(n, nrec)
+        bytes, plus PAYLOAD_PAD for a decode).  Returns (Tree, items,
+        total_bytes).  A HipHuffError of status -5 (capacity) carries .tree,
+        .items and .total_bytes."""
+        import torch
+        assert syms.is_cuda and out.is_cuda and syms.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert syms.is_contiguous() and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(syms.device)
+        offsets = self._ragged_offsets_dev(offsets, syms.device, s)
+        n, nrec = syms.numel(), offsets.numel() - 1
+        tb = _TreeBuf()
+        items = np.zeros((nrec, 4), np.uint64) if host_items else None
+        total = C.c_uint64(0)
+        rc = lib().hh_compress_ragged_device(
+            self._h, syms.data_ptr() if n else None, n, offsets.data_ptr(), nrec, out.data_ptr(), out.numel(),
+            C.byref(tb), self._items_out_ptr(items_out, nrec) if items_out is not None else None,
+            items.ctypes.data if host_items and nrec else None, C.byref(total), s.cuda_stream)
+        if rc == -5:
+            e = HipHuffError(rc, "compress_ragged")
+            e.tree, e.items, e.total_bytes = Tree._from_buf(tb), items, int(total.value)
+            raise e
+        _check(rc, "compress_ragged")
         return Tree._from_buf(tb), items, int(total.value)
 
     def close(self):

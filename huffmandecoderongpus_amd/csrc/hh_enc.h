@@ -1,6 +1,7 @@
 // hh_enc.h -- the encoder handle, shared by csrc/hh_encode.hip (encode,
-// compress), csrc/hh_encb.hip (blocked encode, compress) and csrc/hh_hist.hip
-// (histogram).  Not part of the public ABI.
+// compress), csrc/hh_encb.hip (blocked encode, compress), csrc/hh_encr.hip
+// (ragged blocked encode, compress) and csrc/hh_hist.hip (histogram).  Not
+// part of the public ABI.
 #ifndef HH_ENC_H_
 #define HH_ENC_H_
 

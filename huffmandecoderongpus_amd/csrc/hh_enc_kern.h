@@ -1,7 +1,7 @@
 // hh_enc_kern.h -- what the encoder's kernels share: the chunk geometry, the
 // code table, the workgroup sum, the loads and the image's size
 // (csrc/hh_encode.hip: one stream; csrc/hh_encb.hip: blocks, each its own
-// stream).
+// stream; csrc/hh_encr.hip: records cut at an offsets list).
 #ifndef HH_ENC_KERN_H_
 #define HH_ENC_KERN_H_
 

@@ -329,6 +329,50 @@ int hh_encode_blocks(const hh_tree *t, const uint8_t *syms, uint64_t n, uint64_t
     return HH_OK;
 }
 
+/* Ragged blocked encode on the host (the device form: csrc/hh_encr.hip). */
+uint64_t hh_encode_ragged_bound(const hh_tree *t, uint64_t n, uint64_t nrec) {
+    hh_tree_info in;
+    if (hh_tree_check(t, &in)) return 0;
+    return ((n * (uint64_t)in.maxlen + 7) / 8 + 4 * nrec + 3) / 4 * 4;
+}
+
+int hh_encode_ragged(const hh_tree *t, const uint8_t *syms, uint64_t n, const uint64_t *offs, uint64_t nrec,
+                     uint8_t *out, uint64_t cap, hh_batch_item *items, uint64_t *total_bytes) {
+    if (!t || !total_bytes || !offs || (n && !syms) || (!out && cap)) return HH_ERR_ARG;
+    *total_bytes = 0;
+    codebook cb;
+    int rc = build_codebook(t, &cb);
+    if (rc) return rc;
+    if (offs[0] != 0 || offs[nrec] != n) return HH_ERR_ARG;
+    for (uint64_t r = 0; r < nrec; r++)
+        if (offs[r] > offs[r + 1]) return HH_ERR_ARG;
+    for (uint64_t i = 0; i < n; i++)
+        if (!cb.have[syms[i]]) return HH_ERR_ARG;
+    /* the lengths first: the items, the total, the capacity check */
+    uint64_t off = 0;
+    for (uint64_t r = 0; r < nrec; r++) {
+        uint64_t bits = 0;
+        for (uint64_t i = offs[r]; i < offs[r + 1]; i++) bits += cb.len[syms[i]];
+        if (items) {
+            items[r].data_off = off;
+            items[r].bits = bits;
+            items[r].out_off = offs[r];
+            items[r].cap = offs[r + 1] - offs[r];
+        }
+        off += (bits + 31) / 32 * 4;
+    }
+    *total_bytes = off;
+    if (off > cap) return HH_ERR_CAPACITY;
+    uint64_t at = 0;
+    for (uint64_t r = 0; r < nrec; r++) {
+        const uint64_t bits = encode_with(&cb, syms + offs[r], offs[r + 1] - offs[r], out + at);
+        const uint64_t end = at + (bits + 31) / 32 * 4;
+        at += (bits + 7) / 8;
+        while (at < end) out[at++] = 0;          /* up to the next record's word */
+    }
+    return HH_OK;
+}
+
 /* ------------------------------------------------------------------ */
 /* decode tables (layout in hh_internal.h)                             */
 /* ------------------------------------------------------------------ */

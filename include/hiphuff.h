@@ -20,6 +20,8 @@
  *                                                             stream per call)
  *   hh_encode_blocks*, hh_encoder_encode_blocks, hh_compress_blocks_*
  *                  the batch's producer: blocks of one text, each its own stream
+ *   hh_encode_ragged*, hh_encoder_encode_ragged, hh_compress_ragged_*
+ *                  the same for records of any lengths, cut at an offsets list
  *   hh_stage_*   reference-shaped stage kernels             replaces the six kernels of
  *                                                             ReleaseCL/kernels/ *.cl one by one
  *   hipHuffApproach  plugin with the reference's decoder       decodeUtil.h:14-19 function-pointer
@@ -598,6 +600,73 @@ int hh_compress_blocks_device_items(hh_encoder *enc, const void *d_syms, uint64_
                                     hh_batch_item *d_items /* device, nb */,
                                     hh_batch_item *items /* host, nb, may be NULL */,
                                     uint64_t *total_bytes, void *hip_stream);
+
+/* ---------------------------------------------------------------------- */
+/* Ragged blocked encode: records of any lengths.  n symbols are cut at   */
+/* a list of offsets: offs has nrec + 1 values, offs[0] == 0,             */
+/* nondecreasing, offs[nrec] == n; record r is the symbols                 */
+/* [offs[r], offs[r + 1]) and may be empty.  Every record is encoded on   */
+/* its own from the root, exactly as hh_encode would encode those symbols */
+/* alone -- all of them in one call.                                       */
+/* ---------------------------------------------------------------------- */
+/* Layout: the blocks' (above) with records for blocks.  Record r starts at
+ * byte data_off[r], data_off[0] = 0, data_off[r + 1] = data_off[r] +
+ * ceil(bits[r] / 32) * 4; the bits between a record's end and the next
+ * 4-byte boundary are zero; an empty record has bits 0, takes no bytes and
+ * shares its data_off with its successor.  *total_bytes = data_off[nrec];
+ * nothing is written at or beyond it.  items[r] = {data_off[r], bits[r],
+ * out_off = offs[r], cap = offs[r + 1] - offs[r]}: the list goes unchanged
+ * into hh_decode_batch_device(_items), which gives the text back in place
+ * (any subset of its rows gives those records).  With offs[r] = min(n, r * B)
+ * the bytes, the items and the total are hh_encode_blocks' for block_syms = B.
+ * hh_encode_ragged_bound: bytes that hold the ragged stream of any valid
+ * offs: ceil(n * maxlen / 8) + 4 * nrec, rounded up to 4; 0 for a bad tree.
+ * hh_encode_ragged: the host reference (syms, offs, out, items on the host;
+ * out any alignment; items may be NULL).
+ * hh_encoder_encode_ragged: on the GPU through an encoder (its workspace,
+ * grown on demand).  d_syms, d_offs (nrec + 1 values, 8-byte aligned) and
+ * d_out (4-byte aligned) are device pointers; d_items (device, nrec entries,
+ * 8-byte aligned, may be NULL) and items (host, nrec entries, may be NULL)
+ * receive the list.  With items == NULL nothing per record crosses to the
+ * host: only the totals and the flags come back.  Enqueued on hip_stream,
+ * returns when done, one call at a time per encoder, no device-wide wait,
+ * nothing on the null stream -- as hh_encoder_encode_blocks.
+ * HH_ERR_ARG: a null pointer, d_offs or d_items off an 8-byte or d_out off a
+ * 4-byte boundary; a symbol absent from the tree; an offs that breaks one of
+ * its three rules (found on the device, in the pass over the records) -- the
+ * output is untouched then and *total_bytes = 0.  HH_ERR_CAPACITY:
+ * *total_bytes > cap, found before any byte of the output is written; items,
+ * d_items and *total_bytes are filled (the size to retry with).
+ * HH_ERR_UNSUPPORTED: nrec >= 2^32 - 1, more chunks of 4096 symbols than a
+ * launch's grid holds (n above about 2^36), codes over 64 bits.  n == 0:
+ * offs must be all zero; HH_OK, *total_bytes = 0, nothing written.
+ * Range reads (hh_decode_blocks_read, _gather) need one block_syms and do
+ * not take a ragged list. */
+uint64_t hh_encode_ragged_bound(const hh_tree *tree, uint64_t n, uint64_t nrec);
+int hh_encode_ragged(const hh_tree *tree, const uint8_t *syms, uint64_t n,
+                     const uint64_t *offs /* host, nrec + 1 */, uint64_t nrec, uint8_t *out, uint64_t cap,
+                     hh_batch_item *items /* host, nrec, may be NULL */, uint64_t *total_bytes);
+int hh_encoder_encode_ragged(hh_encoder *enc, const hh_tree *tree, const void *d_syms, uint64_t n,
+                             const uint64_t *d_offs /* device, nrec + 1 */, uint64_t nrec,
+                             void *d_out, uint64_t cap,
+                             hh_batch_item *d_items /* device, nrec, may be NULL */,
+                             hh_batch_item *items /* host, nrec, may be NULL */,
+                             uint64_t *total_bytes, void *hip_stream);
+/* Compress into records: the histogram of all n > 0 bytes, hh_tree_build,
+ * then hh_encoder_encode_ragged with that one tree, which *tree receives
+ * (also with HH_ERR_CAPACITY).  The total bits must equal the histogram's sum
+ * of count x code length, else HH_ERR_INTERNAL.  n == 0 or nrec == 0:
+ * HH_ERR_ARG.  hh_compress_ragged_bound(n, nrec) = (n + 3) / 4 * 4 + 4 * nrec
+ * always suffices, by hh_compress_blocks_bound's argument: the text under
+ * its own Huffman code is at most 8 n bits, and rounding a record up to a
+ * whole word adds less than 4 bytes. */
+uint64_t hh_compress_ragged_bound(uint64_t n, uint64_t nrec);
+int hh_compress_ragged_device(hh_encoder *enc, const void *d_syms, uint64_t n,
+                              const uint64_t *d_offs /* device, nrec + 1 */, uint64_t nrec,
+                              void *d_out, uint64_t cap, hh_tree_buf *tree,
+                              hh_batch_item *d_items /* device, nrec, may be NULL */,
+                              hh_batch_item *items /* host, nrec, may be NULL */,
+                              uint64_t *total_bytes, void *hip_stream);
 
 /* ---------------------------------------------------------------------- */
 /* Segments (multi-GPU shards).  The stream is cut into tiles of           */

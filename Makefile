@@ -22,9 +22,9 @@ CLI      := $(BUILD)/HuffFramework
 EMU      := tests/emu/libhh_emu.so
 # the decoder's .hip units, listed once for `lib` and `variant`, and the
 # objects a variant takes as built
-DEC_UNITS  := hh_device hh_r2 hh_exact hh_host hh_fsm hh_one hh_batch hh_batch_plan hh_batch_read hh_batch_gather
+DEC_UNITS  := hh_device hh_r2 hh_exact hh_host hh_fsm hh_one hh_batch hh_batch_plan hh_batch_read hh_batch_gather hh_batch_take
 DEC_HDRS   := $(addprefix $(CSRC)/,hh_algo.h hh_batch.h hh_batch_algo.h hh_batch_gather_algo.h hh_batch_plan_algo.h \
-              hh_batch_read_algo.h hh_dec.h \
+              hh_batch_read_algo.h hh_batch_take_algo.h hh_dec.h \
               hh_fsm.h hh_fsm_algo.h hh_fsm_dev.h hh_fsm_kern.h hh_internal.h) include/hiphuff.h
 OTHER_OBJS := $(BUILD)/hh_encode.o $(BUILD)/hh_encb.o $(BUILD)/hh_encr.o $(BUILD)/hh_hist.o $(BUILD)/hh_probe.o $(BUILD)/hh_build.o \
               $(BUILD)/hh_plugin.o
@@ -91,13 +91,13 @@ $(BUILD)/ub_fetch: tools/ubench/ub_fetch.hip | $(BUILD)
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $<
 
 $(EMU): tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp tests/emu/hh_batch_emu.cpp tests/emu/hh_batch_plan_emu.cpp \
-        tests/emu/hh_blocks_read_emu.cpp tests/emu/hh_blocks_gather_emu.cpp tests/emu/hh_encr_emu.cpp \
-        $(CSRC)/hh_algo.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_encr_algo.h \
+        tests/emu/hh_blocks_read_emu.cpp tests/emu/hh_blocks_gather_emu.cpp tests/emu/hh_encr_emu.cpp tests/emu/hh_take_emu.cpp \
+        $(CSRC)/hh_batch_take_algo.h $(CSRC)/hh_algo.h $(CSRC)/hh_fsm_algo.h $(CSRC)/hh_encr_algo.h \
         $(CSRC)/hh_batch_algo.h $(CSRC)/hh_batch_gather_algo.h $(CSRC)/hh_batch_plan_algo.h \
         $(CSRC)/hh_batch_read_algo.h $(CSRC)/hh_fsm.h $(CSRC)/hh_internal.h $(BUILD)/hh_huff.o
 	$(CXX) -O2 -fPIC -shared $(INC) -Wno-comment -o $@ tests/emu/hh_emu.cpp tests/emu/hh_fsm_emu.cpp \
 	    tests/emu/hh_batch_emu.cpp tests/emu/hh_batch_plan_emu.cpp tests/emu/hh_blocks_read_emu.cpp \
-	    tests/emu/hh_blocks_gather_emu.cpp tests/emu/hh_encr_emu.cpp $(BUILD)/hh_huff.o
+	    tests/emu/hh_blocks_gather_emu.cpp tests/emu/hh_encr_emu.cpp tests/emu/hh_take_emu.cpp $(BUILD)/hh_huff.o
 
 clean:
 	rm -rf $(BUILD) $(LIB) $(EMU)

@@ -160,6 +160,9 @@ _SIGS = {
     "hh_decode_blocks_gather": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                  C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                                 C.c_int),
+    "hh_decode_batch_take": ([C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hh_decode_take_round_tiles": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     "hh_decode_batch_round_tiles": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     "hh_decoder_tile_bits": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hh_decode_device_range": ([C.c_void_p, C.c_void_p, C.POINTER(_Range), C.c_void_p,
@@ -964,6 +967,71 @@ class Decoder:
             summ.data_ptr() if summ is not None else None, s.cuda_stream)
         _check(rc, what)
         return (read_len, status, summ) if summ is not None else (read_len, status)
+
+    def take_records(self, data, index, ids, out, out_offs=None, status=None, summary=False, stream=None,
+                     data_bytes: Optional[int] = None, out_bytes: Optional[int] = None) -> tuple:
+        """hh_decode_batch_take: the records of a coded column named by ids,
+        their bytes one after another in out and the offsets that delimit
+        them, enqueued on stream (default: the current one) without
+        synchronising.  data: the records' payload; index: the CUDA int64
+        (nrec, 4) tensor Encoder.encode_ragged(..., items_out=t) (or
+        encode_blocks) fills; ids: a CUDA int64 tensor of m record ids
+        (uint64 values viewed as int64; a host array is uploaded on the
+        call's stream), None: all records in order.  out_offs (int64, m + 1),
+        status (int32, m) and summary as in decode_batch_items.  Returns
+        (out_offs, status[, summary]), complete once the stream has passed
+        the call's work.  A bad id or index row gets status -1 and length 0,
+        a record past out's end -2, one whose stream and length disagree -3,
+        and the others decode; only what the host can check raises.  The
+        tensors are kept alive until the next batch call on this decoder or
+        close()."""
+        import torch
+        assert data.is_cuda and out.is_cuda and data.dtype == torch.uint8 and out.dtype == torch.uint8
+        assert data.is_contiguous() and out.is_contiguous()
+        if not (index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 2
+                and index.shape[1] == 4):
+            raise ValueError("index: a contiguous CUDA int64 tensor of (data_off, bits, out_off, cap) rows")
+        nrec = index.shape[0]
+        s = stream if stream is not None else torch.cuda.current_stream(data.device)
+        if ids is not None and not torch.is_tensor(ids):
+            h = np.ascontiguousarray(ids).astype(np.uint64, copy=False).view(np.int64).reshape(-1)
+            with torch.cuda.stream(s):
+                ids = torch.from_numpy(h).to(data.device, non_blocking=True)
+        if ids is not None and not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.dim() == 1):
+            raise ValueError("ids: a contiguous CUDA int64 tensor of record ids, or None")
+        m = nrec if ids is None else ids.shape[0]
+        with torch.cuda.stream(s):
+            if out_offs is None:
+                out_offs = torch.empty(m + 1, dtype=torch.int64, device=data.device)
+            if status is None:
+                status = torch.empty(m, dtype=torch.int32, device=data.device)
+            if summary is True:
+                summ = torch.empty(6, dtype=torch.int32, device=data.device)
+            else:
+                summ = None if summary is False or summary is None else summary
+        assert summ is None or (summ.is_cuda and summ.dtype == torch.int32 and summ.is_contiguous()
+                                and summ.numel() == 6)
+        assert out_offs.is_cuda and out_offs.dtype == torch.int64 and out_offs.is_contiguous() \
+            and out_offs.numel() == m + 1
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == m
+        self._batch_keep = (data, index, ids, out, out_offs, status, summ)
+        rc = lib().hh_decode_batch_take(
+            self._h, data.data_ptr(), data.numel() if data_bytes is None else data_bytes,
+            # (an empty list of ids reads no index: nrec 0 beside the NULL of an empty tensor)
+            index.data_ptr() if nrec and m else None, nrec if m else 0, ids.data_ptr() if ids is not None and m else None, m,
+            out.data_ptr(), out.numel() if out_bytes is None else out_bytes,
+            out_offs.data_ptr() if m else None, status.data_ptr() if m else None,
+            summ.data_ptr() if summ is not None else None, s.cuda_stream)
+        _check(rc, "take_records")
+        return (out_offs, status, summ) if summ is not None else (out_offs, status)
+
+    def take_round_tiles(self) -> int:
+        """hh_decode_take_round_tiles: tiles per round of take_records'
+        kernel for the current tree (a round holds 64 x tiles regions of
+        geometry()["S"] bits, of as many records as fall into them)."""
+        w = C.c_uint32(0)
+        _check(lib().hh_decode_take_round_tiles(self._h, C.byref(w)), "take_round_tiles")
+        return int(w.value)
 
     @staticmethod
     def batch_summary(summary) -> dict:

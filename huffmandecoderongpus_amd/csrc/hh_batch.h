@@ -42,6 +42,8 @@ struct BatchDev {
     hipEvent_t end;          // recorded after its last kernel (0: not created yet)
     int pend;                // 1: recorded and not known to have passed
     hipStream_t pend_st;     // its stream
+    // the record take's kernel (hh_batch_take.hip): its resident workgroups for tk_W waves and tk_lds bytes
+    uint32_t tk_W, tk_lds, tk_grid;
 };
 
 // What a round's kernels share (k_batch, hh_batch.hip; k_gather,
@@ -177,5 +179,14 @@ int batch_decode_gather(BatchDev *b, const FsmDev *fd, const void *d_data, uint6
                         const hh_block_read *d_reads, uint64_t m, uint32_t P, uint32_t nb, void *d_out,
                         uint64_t out_bytes, uint64_t *d_read_len, int32_t *d_status, hh_batch_summary *d_summary,
                         hipStream_t st);
+
+// hh_batch_take.hip: the record take (hh_decode_batch_take) -- the plan over
+// the taken records, k_take's packed rounds, the summary; all enqueued on st.
+// batch_take_waves: k_take's waves per workgroup and LDS bytes for the tree.
+int batch_decode_take(BatchDev *b, const FsmDev *fd, const void *d_data, uint64_t data_bytes,
+                      const hh_batch_item *d_index, uint64_t nrec, const uint64_t *d_ids, uint64_t m, void *d_out,
+                      uint64_t out_bytes, uint64_t *d_out_offs, int32_t *d_status, hh_batch_summary *d_summary,
+                      hipStream_t st);
+int batch_take_waves(const BatchDev *b, const FsmDev *fd, uint32_t *W, uint32_t *lds);
 
 #endif

@@ -590,6 +590,38 @@ extern "C" int hh_decode_blocks_gather(hh_decoder *d, const void *d_data, uint64
     return HH_OK;
 }
 
+// The record take: the host sees neither the ids nor the index; the rest is
+// the plan's kernels' (hh_batch_take.hip).
+extern "C" int hh_decode_batch_take(hh_decoder *d, const void *d_data, uint64_t data_bytes,
+                                    const hh_batch_item *d_index, uint64_t nrec, const uint64_t *d_ids, uint64_t m,
+                                    void *d_out, uint64_t out_bytes, uint64_t *d_out_offs, int32_t *d_status,
+                                    hh_batch_summary *d_summary, void *hip_stream) {
+    if (!d) return HH_ERR_ARG;
+    if (!d_ids && m != nrec) return HH_ERR_ARG;
+    if (m == 0) {
+        if (!d_summary) return HH_OK;
+        HIP_OK(hipSetDevice(d->device));
+        return batch_summary_clear(d_summary, (hipStream_t)hip_stream);
+    }
+    if (!d_out_offs || !d_status || !d_data || !d_out || (!d_index && nrec > 0) || !d->have_tree) return HH_ERR_ARG;
+    if (((uintptr_t)d_data & 3u) != 0 || ((uintptr_t)d_out_offs & 7u) != 0) return HH_ERR_ARG;   // word, 64-bit accesses
+    if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;
+    HIP_OK(hipSetDevice(d->device));
+    const int rc = batch_decode_take(&d->batch, &d->fsm, d_data, data_bytes, d_index, nrec, d_ids, m, d_out, out_bytes,
+                                     d_out_offs, d_status, d_summary, (hipStream_t)hip_stream);
+    if (rc != HH_OK) return rc;
+    memset(&d->stats, 0, sizeof(d->stats));                // (the host knows no lengths)
+    d->stats.state_machine = 3;
+    return HH_OK;
+}
+
+extern "C" int hh_decode_take_round_tiles(const hh_decoder *d, uint32_t *tiles) {
+    if (!d || !tiles || !d->have_tree) return HH_ERR_ARG;
+    if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;
+    uint32_t lds = 0;
+    return batch_take_waves(&d->batch, &d->fsm, tiles, &lds);
+}
+
 extern "C" int hh_decode_batch_round_tiles(const hh_decoder *d, uint32_t *tiles) {
     if (!d || !tiles || !d->have_tree) return HH_ERR_ARG;
     if (!d->fsm.ok || !d->batch.ok) return HH_ERR_UNSUPPORTED;

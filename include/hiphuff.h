@@ -524,6 +524,61 @@ int hh_decode_blocks_gather(hh_decoder *dec, const void *d_data, uint64_t data_b
                             hh_batch_summary *d_summary /* device, may be NULL */,
                             void *hip_stream);
 
+/* Record take: the records of a coded column named by a list of ids, their
+ * bytes one after another in d_out and the offsets that delimit them -- an
+ * Arrow `take` on a string column, a gather of rows by id.  d_index is the
+ * list hh_encoder_encode_ragged (or hh_encoder_encode_blocks_items: take by
+ * block id) leaves on the device; of an entry only data_off, bits and cap --
+ * the record's length in symbols -- are read, out_off is ignored.  d_ids: m
+ * record ids (NULL: the records 0 .. nrec - 1 in order, m == nrec); ids may
+ * repeat and come in any order.
+ * For taken record j, r = d_ids[j]: len_j = d_index[r].cap when r < nrec and
+ * the entry keeps the payload rules (data_off a multiple of 4; for bits > 0,
+ * data_off + ceil(bits/8) + HH_PAYLOAD_PAD <= data_bytes, no sum
+ * overflowing); else len_j = 0, d_status[j] = HH_ERR_ARG and the record
+ * reads and writes nothing.  d_out_offs[j] = the sum of len_i over i < j,
+ * d_out_offs[m] the total, saturating; all m + 1 are written whatever the
+ * statuses (a caller whose buffer was too small reads the size it needs in
+ * d_out_offs[m]).  A record with d_out_offs[j + 1] > out_bytes gets
+ * HH_ERR_CAPACITY and is not decoded; those before it that fit decode.
+ * Otherwise the record's stream is decoded from the root, exactly as
+ * hh_decode_device decodes it alone (tail rule included), to d_out +
+ * d_out_offs[j]: holding c symbols, HH_OK when c == len_j, else
+ * HH_ERR_FORMAT (index and data disagree); in both cases exactly the first
+ * min(c, len_j) symbols are delivered and the rest of the record's range is
+ * untouched.  No byte is stored outside [d_out_offs[j], d_out_offs[j + 1])
+ * for record j, none at or beyond d_out + out_bytes, and no wide store
+ * covers a byte that is not the call's; d_out may have any alignment.  An
+ * empty record (bits == 0, cap == 0) is HH_OK.
+ * d_summary: total_len the sum of len_j over the HH_OK records; n_failed,
+ * first_failed, first_status as in hh_decode_batch_device_items, whose empty
+ * summary m == 0 gives (and enqueues nothing else).
+ * Many records share a round of the decode kernel (64 x tiles lanes, a lane
+ * per region of hh_decoder_tile_bits() / 64 bits: hh_decode_take_round_tiles),
+ * so short records cost their bits, not a round each.
+ * Stream order, the decoder's end event, the batch workspace (80 bytes per
+ * taken record and some) and hh_stats: hh_decode_batch_device_items' rules,
+ * word for word -- everything on hip_stream, no synchronisation, no
+ * device-to-host copy, nothing on the null stream but where the workspace
+ * must grow; d_ids and d_index are read by the call's first kernel only.
+ * Host checks: HH_ERR_ARG for a null pointer with m > 0 (d_summary and d_ids
+ * excepted; d_index only when nrec > 0), d_data off a 4-byte or d_out_offs
+ * off an 8-byte boundary, no tree set, d_ids == NULL with m != nrec;
+ * HH_ERR_UNSUPPORTED for a tree the batch cannot take, m or nrec >= 2^32 - 1. */
+int hh_decode_batch_take(hh_decoder *dec, const void *d_data, uint64_t data_bytes,
+                         const hh_batch_item *d_index /* device, nrec */, uint64_t nrec,
+                         const uint64_t *d_ids /* device, m; NULL: records 0..nrec-1 in order, m == nrec */,
+                         uint64_t m,
+                         void *d_out, uint64_t out_bytes,
+                         uint64_t *d_out_offs /* device, m + 1 */,
+                         int32_t *d_status /* device, m */,
+                         hh_batch_summary *d_summary /* device, may be NULL */,
+                         void *hip_stream);
+/* The tiles per round of the take's kernel for the current tree (its marks
+ * take LDS the batched decode does not need: for some trees one tile fewer
+ * than hh_decode_batch_round_tiles). */
+int hh_decode_take_round_tiles(const hh_decoder *dec, uint32_t *tiles);
+
 /* ---------------------------------------------------------------------- */
 /* Blocked encode: the producer of a batch. n symbols are cut into       */
 /* nb = ceil(n / block_syms) blocks, block b the symbols                  */
@@ -640,8 +695,9 @@ int hh_compress_blocks_device_items(hh_encoder *enc, const void *d_syms, uint64_
  * HH_ERR_UNSUPPORTED: nrec >= 2^32 - 1, more chunks of 4096 symbols than a
  * launch's grid holds (n above about 2^36), codes over 64 bits.  n == 0:
  * offs must be all zero; HH_OK, *total_bytes = 0, nothing written.
- * Range reads (hh_decode_blocks_read, _gather) need one block_syms and do
- * not take a ragged list. */
+ * The consumer at this grain is hh_decode_batch_take: chosen records,
+ * packed.  Range reads by byte offset (hh_decode_blocks_read, _gather) still
+ * need one block_syms and do not take a ragged list. */
 uint64_t hh_encode_ragged_bound(const hh_tree *tree, uint64_t n, uint64_t nrec);
 int hh_encode_ragged(const hh_tree *tree, const uint8_t *syms, uint64_t n,
                      const uint64_t *offs /* host, nrec + 1 */, uint64_t nrec, uint8_t *out, uint64_t cap,
